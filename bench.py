@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: agent-steps/s of the fused swarm step at N=64 drones x E=8192 envs/GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|n16|n256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|n16|n256] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line (the headline figure, its
+`ms_per_step` and the roofline fields that come from the timed region itself).  `--full` adds the
+legs that take runs of their own: the eager per-launch event pass, the policy kernel alone
+(`--policy`) and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step returned
+(obs, reward, terminated, truncated, env_done, ...) as DIR/<name>.npy: the timed region then starts
+from the state the W warm-up steps left, so equal arguments give equal files.
 
 `--gpus N` alone (no WORLD_SIZE in the environment) makes this process a launcher: it spawns N
 rank processes of this file, one per GPU, before touching the GPU itself, forwards rank 0's JSON
@@ -24,14 +32,14 @@ K > 256 steps are replayed from a hipGraph holding one launch per action tensor 
 rate without per-step host launch cost); short regions (the driver's K = 20) are launched eagerly
 (host launches run ahead of the GPU; a replayed graph's kernels measured slower there); HIP events recorded on the launch stream around that
 timed region give the average launch duration (`roofline.kernel_ms_mean`, the roofline's time
-base; compare `rocprofv3 --kernel-trace --stats` in profiles/).  A second, eager pass with one
-event pair per launch is reported as `ms_per_step_eager` / `kernel_ms_eager_events`.
+base; compare `rocprofv3 --kernel-trace --stats` in profiles/).  With `--full` a second, eager pass
+with one event pair per launch is reported as `ms_per_step_eager` / `kernel_ms_eager_events`.
 `--ctde` also emits the CTDE global_state and, with several ranks, all-gathers it every
 `--gather-every` steps over RCCL on a side stream, overlapped with the following steps (a
 `--gs-slots` device ring; swarm_marl_amd.distributed.GlobalStateGather; config 5; eager timing).
 Under SWARM_BENCH_REHEARSAL (gloo, every rank on cuda:0) the gather is staged through host memory.
 
-`cpu_baseline` = the C port of the reference step (oracle/swarm_oracle.c) on the host cores for
+With `--full`: `cpu_baseline` = the C port of the reference step (oracle/swarm_oracle.c) on the host cores for
 a bounded sample of the same workload; `cpu_baseline_variants` = the per-agent loop restatement
 (like the reference `DroneSwarmEnv.step`) and the vectorised NumPy restatement, one process per
 core.
@@ -95,7 +103,17 @@ def parse(argv=None):
                     help="timed seconds of the C-port CPU baseline")
     ap.add_argument("--cpu-variant-seconds", type=float, default=3.0,
                     help="timed seconds of each Python restatement variant (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the eager pass with one event pair "
+                         "per launch (ms_per_step_eager, roofline.kernel_ms_eager_events / kernel_ms_per_launch), "
+                         "the policy kernel alone (--policy: policy.kernel_ms_mean and its roofline) and the "
+                         "CPU baselines (cpu_baseline, cpu_baseline_variants)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all: a fixed, seeded sample of the envs when the batch "
+                         "is larger, its indices in env_index.npy).  The timed region then starts from the "
+                         "state the W warm-up steps left, so the files repeat from run to run")
     ap.add_argument("--waves-per-simd", type=int, default=0,
                     help="persistent step kernel: resident waves per SIMD (0 = library default)")
     ap.add_argument("--no-persistent", action="store_true",
@@ -256,6 +274,30 @@ def gather_schedule(steps: int, every: int) -> list[int]:
     if steps and (not ks or ks[-1] != steps - 1):
         ks.append(steps - 1)
     return ks
+
+
+REHEARSE_MAX_S = 5.0  # one-rank runs stop rehearsing the K-step region after this many seconds
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: budget of the files together (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, named, envs: int, rank: int, world: int) -> None:
+    """--dump-outputs: write the [E, ...] tensors of `named` (name, tensor or None) as float32
+    <name>.npy under `out_dir` (<name>.rank<r>.npy with several ranks).  When they exceed
+    DUMP_MAX_BYTES together, the rows of a fixed sample of the envs (seeded, sorted; the same for
+    every tensor), whose indices go to env_index.npy."""
+    import torch
+    named = [(name, t) for name, t in named if t is not None]
+    per_env = sum(t[0].numel() * 4 for _, t in named) + 8
+    keep = min(envs, max(1, DUMP_MAX_BYTES // per_env))
+    idx = np.sort(np.random.default_rng(2024).choice(envs, size=keep, replace=False)) if keep < envs \
+        else np.arange(envs)
+    sel = torch.as_tensor(idx, device=named[0][1].device)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = f".rank{rank}" if world > 1 else ""
+    np.save(d / f"env_index{tag}.npy", idx.astype(np.float64))
+    for name, t in named:
+        np.save(d / f"{name}{tag}.npy", t.index_select(0, sel).to(torch.float32).cpu().numpy())
 
 
 # ----------------------------------------------------------------------------- CPU baselines
@@ -529,6 +571,11 @@ def main(argv=None):
     for k in range(args.warmup):
         step(k)
     sync()
+    # --dump-outputs: the untimed steps between here and the timed region are counted by the clock
+    # (device warm-up), so the timed region restarts from this state (and obs: the policy reads it)
+    snap = None
+    if args.dump_outputs:
+        snap = [(t, t.clone()) for t in (*vec.state_dict().values(), vec.obs)]
 
     # With env groups the timed region is bracketed on group stream 0 (the other groups fork
     # from and join into it): the null stream, which may share a hardware queue with a group
@@ -745,11 +792,27 @@ def main(argv=None):
         sync()
         warm_ms = (time.perf_counter() - t0) * 1e3
     pre = start_events if (not use_graph and args.events_before) else None
+    rehearsals = 0
     if gatherer is None:
+        t_reh = time.perf_counter()
         for _ in range(max(0, args.rehearse)):
             timed_region(body, world, sync, pre=pre)
+            rehearsals += 1
+            # one rank: regions of seconds (K in the 1e5s) are in a loop of such regions after the
+            # first; no more rehearsals once they have taken REHEARSE_MAX_S (ranks must agree on
+            # the count, so several ranks run them all)
+            if world == 1 and time.perf_counter() - t_reh > REHEARSE_MAX_S:
+                break
     gather_t0 = gatherer.k if gatherer is not None else 0
+    if snap is not None:
+        sync()
+        for t, saved in snap:
+            t.copy_(saved)
     wall = timed_region(body, world, sync, spin=t_ev[1] if args.spin_sync else None, pre=pre)
+    if args.dump_outputs:  # before any later pass steps the envs again
+        named = [(name, getattr(vec, name)) for name in
+                 ("obs", "reward", "terminated", "truncated", "env_done", "global_state", "dist_goal", "info_flags")]
+        dump_outputs(args.dump_outputs, named + [("policy_actions", pol_act)], e, rank, world)
     walls_rep = [wall]
     for _ in range(args.region_reps - 1):  # diagnostic repeats (not reported as the value)
         walls_rep.append(timed_region(body, world, sync, pre=pre))
@@ -760,11 +823,11 @@ def main(argv=None):
     else:
         kern_ms = t_ev[0].elapsed_time(t_ev[1]) / args.steps
 
-    # ---- diagnostic pass: eager launches, one event pair around every launch on its stream
+    # ---- diagnostic pass (--full): eager launches, one event pair around every launch on its stream
     # (with env groups the launches of a step overlap: the per-launch mean is what rocprofv3
     # reports per dispatch, the whole pass / K is the eager step time)
     ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(args.steps)] for _ in range(G)]
+           for _ in range(args.steps if args.full else 0)] for _ in range(G)]
     ev_all = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     streams_g = vec.group_streams if G > 1 else [stream]
 
@@ -786,12 +849,14 @@ def main(argv=None):
                     ev[g][k][1].record(st)
         join()
         ev_all[1].record(stream)
-    wall_eager = timed_region(body_eager, world, sync)
-    kern_launch = float(np.mean([a.elapsed_time(b) for row in ev for a, b in row]))
-    kern_eager = ev_all[0].elapsed_time(ev_all[1]) / args.steps
+    wall_eager = kern_launch = kern_eager = 0.0
+    if args.full:
+        wall_eager = timed_region(body_eager, world, sync)
+        kern_launch = float(np.mean([a.elapsed_time(b) for row in ev for a, b in row]))
+        kern_eager = ev_all[0].elapsed_time(ev_all[1]) / args.steps
 
     pol_ms = 0.0
-    if pol is not None:  # the policy kernel alone, K launches on the current obs, events around them
+    if pol is not None and args.full:  # the policy kernel alone, K launches on the current obs, events around them
         pe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         sync()
         cs = torch.cuda.current_stream(dev)
@@ -841,11 +906,12 @@ def main(argv=None):
                                      f"forked to and joined from the {G} group streams ("
                                      f"{'graph replays' if use_graph else 'eager launches'}), / K = whole-batch "
                                      f"step time ({G} overlapping launches of E/{G} envs per step); max over ranks"),
-                "kernel_ms_eager_events": kern_eager_max,
-                "kernel_ms_per_launch": launch_max,
-                "kernel_ms_per_launch_timing": "eager pass, HIP events around each launch on its own "
-                                               "stream, mean (compare rocprofv3 per-dispatch average"
-                                               + (f"; the {G} launches of a step overlap" if G > 1 else "") + ")",
+                **({"kernel_ms_eager_events": kern_eager_max,
+                    "kernel_ms_per_launch": launch_max,
+                    "kernel_ms_per_launch_timing": "eager pass, HIP events around each launch on its own "
+                                                   "stream, mean (compare rocprofv3 per-dispatch average"
+                                                   + (f"; the {G} launches of a step overlap" if G > 1 else "") + ")"}
+                   if args.full else {}),
                 "kernel": vec.kernel_name(),
                 "grid": int(vec.group_launch_info[0].blocks),
                 "env_groups": G, "launches_per_step": G}
@@ -878,9 +944,10 @@ def main(argv=None):
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall_max / args.steps * 1e3,
             **({"ms_per_step_reps": [round(w / args.steps * 1e3, 6) for w in walls_rep]}
                if args.region_reps > 1 else {}),
-            "ms_per_step_eager": eager_max / args.steps * 1e3, "step_timing": timing,
+            **({"ms_per_step_eager": eager_max / args.steps * 1e3} if args.full else {}),
+            "step_timing": timing, "full": args.full,
             "device_warmup": {"ms": round(warm_ms, 1), "steps": warm_steps,
-                              "rehearsals": max(0, args.rehearse) if gatherer is None else 0,
+                              "rehearsals": rehearsals,
                               "note": "untimed replays after the W warm-up steps, then untimed runs of the "
                                       "whole K-step region (rehearsals), before the timed region"},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -910,14 +977,15 @@ def main(argv=None):
         if pol is not None:
             rows = e * n
             flops = 2.0 * rows * (pol.in_dim * 256 + 256 * 256 + 256 * pol.out_dim)
-            tf = flops / (pol_max * 1e-3) / 1e12
             rec["policy"] = {"precision": args.policy, "kernel": f"policy_mlp_{args.policy}",
                              "rows_per_launch": rows, "algorithmic_flops_per_launch": flops,
-                             "kernel_ms_mean": pol_max,
-                             "roofline": {"bound": "mfma", "achieved": tf,
-                                          "peak": MFMA_PEAK_TFLOPS[args.policy], "unit": "TFLOP/s",
-                                          "frac": tf / MFMA_PEAK_TFLOPS[args.policy]},
                              "weights": "random-init TorchFC [256, 256] relu (no checkpoint)"}
+            if args.full:  # the policy kernel's own pass
+                tf = flops / (pol_max * 1e-3) / 1e12
+                rec["policy"].update({"kernel_ms_mean": pol_max,
+                                      "roofline": {"bound": "mfma", "achieved": tf,
+                                                   "peak": MFMA_PEAK_TFLOPS[args.policy], "unit": "TFLOP/s",
+                                                   "frac": tf / MFMA_PEAK_TFLOPS[args.policy]}})
             rec["roofline"]["note"] = "env-step roofline fields cover the whole rollout step"
         if tracker is not None:
             rec["eval"] = {"tracker": ("EvalTracker fused into the step launches (swarm_step64_eval_once: episode "
@@ -925,7 +993,7 @@ def main(argv=None):
                                        "EvalTracker: swarm_eval_update per env group after its step (episode "
                                        "reward, path length, exact formation error, votes, records)"),
                            "fused": tracker.fused, "updates": tracker.updates}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             rec["cpu_baseline"] = cpu_baseline_port(n, e, args.cpu_seconds, raw, args.dynamics == "physics")
             if args.cpu_variant_seconds > 0 and not args.no_term and args.dynamics == "kinematic":
                 rec["cpu_baseline_variants"] = cpu_python_variants(n, e, args.cpu_variant_seconds)
