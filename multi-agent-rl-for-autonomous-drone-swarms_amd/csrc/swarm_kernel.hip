@@ -231,8 +231,10 @@ __device__ __forceinline__ uint32_t med3u(uint32_t a, uint32_t b, uint32_t c) {
   return r;
 }
 // 1/n for the formation mean (np.mean over the n_active - 1 partner terms): v_rcp_f32 (1 ulp)
-// instead of an f64 division; the mean is then within ~1e-7 relative, inside the 1e-5 reward
-// contract (the terms themselves carry d~ = v_sqrt_f32 distances).
+// instead of an f64 division.  The mean is then within 2^-23 relative of the exact quotient, i.e.
+// the reward within 2^-23 x kf x sqrt(3) x world_size absolute (6.2e-7 at the default 0.15 / 20):
+// one part of the reward budget of DESIGN.md §5, whose contract is 1e-5 ABSOLUTE against the f64
+// oracle (the terms themselves carry d~ = v_sqrt_f32 distances, a larger part).
 __device__ __forceinline__ double inv_count(int n) { return (double)__builtin_amdgcn_rcpf((float)n); }
 // Insert key into the ascending list k[0..S-1] (drops the largest): one med3 per slot.
 template <int S>
@@ -327,8 +329,11 @@ __device__ __forceinline__ uint32_t own_pair(uint32_t (&nk)[KS > 0 ? KS : 1], fl
   if constexpr (KS > 0) kins<KS>(nk, (__float_as_uint(v) & keep) | low);
   if constexpr (PASS != 0 && (!FAST || KS == 0)) smin = fminf(smin, (FAST || pr) ? v : __builtin_inff());
   if constexpr (PASS == 1) {
-    // formation uses d_ij widened to double in the reference; d~ keeps the mean within ~1e-6
-    // relative, far inside the 1e-5 reward contract.
+    // formation uses d_ij widened to double in the reference; d~ is within 2^-21 relative of
+    // d_ij and the f32 subtraction adds 2^-24 |d~ - d*|, so the mean of the terms is off by at
+    // most (2^-21 + 2^-24) x sqrt(3) x world_size and the reward by kf times that, absolute
+    // (2.8e-6 at the defaults; it grows with world_size): the largest part of the budget of the
+    // 1e-5 absolute reward contract.
     float e = fabsf(v - ds);
     if constexpr (!FAST) e = pr ? e : 0.f;
     esum += e;
@@ -1560,8 +1565,12 @@ __device__ __forceinline__ void pair_pass_s64(const float* __restrict__ soa, int
   float macc = 0.f;
   // the formation sum: one f32 chain over the pass (own terms group by group, the travelled mirror
   // sum, rotation 32), widened once — the f64 add per 4-rotation group cost a conversion and an
-  // f64 add (both half rate) each; the sum's rounding stays ~1e-6 of the reward (1e-5 contract,
-  // the mirror sum was already one f32 chain)
+  // f64 add (both half rate) each.  Worst-case rounding of the whole chain: 832 x 2^-24 x sqrt(3)
+  // x world_size over the 63 terms, i.e. kf x 13.2 x 2^-24 x sqrt(3) x world_size absolute in the
+  // reward (4.1e-6 at the defaults) against 9.0 (2.8e-6) for the generic kernel's per-group
+  // widening, the mirror sum being one 31-term f32 chain in both.  The contract is 1e-5 absolute
+  // against the f64 oracle; measured, the two kernels stay within 1e-6 of each other up to
+  // world_size 100 (budget and measured maxima: DESIGN.md §5, tests/test_gpu_spec_params.py)
   using FS = typename std::conditional<SWARM_S64_F32SUM != 0, float, double>::type;
   FS fs = 0;
   // every caller starts the pass with an empty key list (F0 = 0)
