@@ -318,6 +318,64 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
 const char* swarm_policy_last_error(void);
 
 /*
+ * On-device centralized critic (the reference's CTDE value function: CentralizedCriticModel's
+ * `value_model`, a TorchFC [256, 256] on global_state of width G = 6N + 3 with one output;
+ * src/swarm_marl/training/models.py):
+ *     value[r] = W3 relu(W2 relu(W1 gs[r] + b1) + b2) + b3
+ * over rows of global_state read in place (swarm_out_t.global_state, or any [rows, in_dim] f32
+ * block).  precision: SWARM_POLICY_BF16 (bf16 MFMA operands, f32 accumulation; W1 streams from
+ * L2 in fragment order) or SWARM_POLICY_F32 (f32 products and sums); SWARM_POLICY_F32X3 is
+ * rejected with SWARM_ELIMIT.
+ */
+#define SWARM_CRITIC_MAX_IN 1539    /* 6 * 256 + 3 */
+
+typedef struct swarm_critic {
+  int32_t in_dim;        /* global_state width G */
+  int32_t precision;     /* SWARM_POLICY_BF16 / SWARM_POLICY_F32 */
+  const void* weights;   /* device copy of the swarm_critic_pack blob (16-B aligned) */
+} swarm_critic_t;
+
+/* Bytes of the packed weight blob (negative SWARM_E* code if unsupported). */
+long long swarm_critic_packed_bytes(int in_dim, int precision);
+
+/* Pack row-major f32 weights (PyTorch layout: w1 [256,in], w2 [256,256], w3 [1,256]) into the
+ * kernel's blob at host_out (host memory). */
+int swarm_critic_pack(int in_dim, int precision, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* w3, const float* b3, void* host_out);
+
+/* value [rows] for gs [rows,in_dim]; async on hip_stream, no allocation, no sync.  rows == 0 is a
+ * no-op. */
+int swarm_critic_forward(const swarm_critic_t* c, const float* gs, long long rows, float* value, void* hip_stream);
+
+const char* swarm_critic_last_error(void);
+
+/*
+ * RLlib TorchDiagGaussian.logp of `actions` [rows,adim] under logits [rows,2*adim] = [mean | log_std]:
+ *     logp = sum_k(-0.5 z_k^2 - log_std_k) - 0.5 adim log(2 pi),   z_k = (a_k - mean_k) exp(-log_std_k)
+ * (the unclipped sampled action, as RLlib stores it).  Async; errors via swarm_critic_last_error.
+ */
+int swarm_gaussian_logp(const float* logits, const float* actions, long long rows, int adim, float* logp,
+                        void* hip_stream);
+
+/*
+ * Generalized advantage estimation over a fragment of T steps of E envs x N agents.  One thread
+ * per (e, n) walks t = T-1 .. 0 in f32, in exactly this order (no fused multiply-add):
+ *     gl = gamma * lam;  carry = 0
+ *     if !valid[t,e,n]: advantage = value_target = 0; carry = 0; continue
+ *     done  = terminated[t,e,n] | truncated[t,e,n] | (env_done[t,e] & (TERMINATED | TRUNCATED)) != 0
+ *     nv    = done ? 0 : value[t+1,e];   prev = done ? 0 : carry
+ *     delta = (reward[t,e,n] + gamma * nv) - value[t,e]
+ *     carry = delta + gl * prev
+ *     advantage[t,e,n] = carry;  value_target[t,e,n] = carry + value[t,e]
+ * value [T+1,E] is V(global_state) before step t, shared by the env's agents; row T bootstraps
+ * the fragment end.  Any episode end (the agent's own termination or truncation, or the env's
+ * __all__) stops the bootstrap.  Async; errors via swarm_critic_last_error.
+ */
+int swarm_gae(const float* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated,
+              const uint8_t* env_done, const uint8_t* valid, int T, int E, int N, float gamma, float lam,
+              float* advantage, float* value_target, void* hip_stream);
+
+/*
  * On-device evaluation metrics: the per-episode summary of
  * scripts/evaluate_protocol.py:237-331 (`_run_single_episode_multi_agent`; formation error
  * :103-116) accumulated on the device from a step's outputs (obs, reward, info_flags, env_done:

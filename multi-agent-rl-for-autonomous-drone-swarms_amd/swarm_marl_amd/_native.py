@@ -53,6 +53,7 @@ POLICY_F32 = 1
 POLICY_F32X3 = 2
 POLICY_ACT_MEAN = 0
 POLICY_ACT_SAMPLE = 1
+CRITIC_MAX_IN = 1539
 EVAL_LIVE = 1
 EVAL_COLLIDED = 2
 EVAL_STEP_FUSED = 1
@@ -66,7 +67,11 @@ EXPORTED_SYMBOLS = (
     "swarm_policy_packed_bytes", "swarm_policy_pack", "swarm_policy_forward", "swarm_policy_last_error",
     "swarm_eval_begin", "swarm_eval_update", "swarm_eval_single_update", "swarm_eval_last_error",
     "swarm_env_cfg_set",
+    "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
+    "swarm_gaussian_logp", "swarm_gae",
 )
+# the rollout half (csrc/swarm_critic.hip); a diagnostic build given by path may leave the unit out
+ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-6:]
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -146,6 +151,10 @@ class SwarmPolicy(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("weights", ctypes.c_void_p)]
 
 
+class SwarmCritic(ctypes.Structure):
+    _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
 class SwarmEval(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in
                 ("ep_reward", "ep_steps", "reached_step", "status", "fe_sum", "start", "goal", "last",
@@ -219,6 +228,20 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.swarm_eval_last_error.argtypes = []
     lib.swarm_env_cfg_set.restype = ctypes.c_int
     lib.swarm_env_cfg_set.argtypes = [P, ctypes.POINTER(SwarmEnvOverrides), vp, vp, vp]
+    if path is None or all(hasattr(lib, name) for name in ROLLOUT_SYMBOLS):
+        lib.swarm_critic_packed_bytes.restype = ctypes.c_longlong
+        lib.swarm_critic_packed_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.swarm_critic_pack.restype = ctypes.c_int
+        lib.swarm_critic_pack.argtypes = [ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, vp]
+        lib.swarm_critic_forward.restype = ctypes.c_int
+        lib.swarm_critic_forward.argtypes = [ctypes.POINTER(SwarmCritic), vp, ctypes.c_longlong, vp, vp]
+        lib.swarm_critic_last_error.restype = ctypes.c_char_p
+        lib.swarm_critic_last_error.argtypes = []
+        lib.swarm_gaussian_logp.restype = ctypes.c_int
+        lib.swarm_gaussian_logp.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_int, vp, vp]
+        lib.swarm_gae.restype = ctypes.c_int
+        lib.swarm_gae.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                  ctypes.c_float, ctypes.c_float, vp, vp, vp]
     got = lib.swarm_abi_version()
     if got != ABI_VERSION:
         raise NativeLibraryError(f"{p}: ABI version {got}, expected {ABI_VERSION}")
@@ -229,12 +252,13 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 
 def check(rc: int, lib: ctypes.CDLL | None = None, policy: bool = False, which: str | None = None) -> None:
     """Raise on a negative return code (bad arguments -> ValueError, HIP errors -> RuntimeError).
-    `which` names the component whose last-error string explains it ("policy", "eval")."""
+    `which` names the component whose last-error string explains it ("policy", "eval", "critic")."""
     if rc == SWARM_OK:
         return
     lib = lib or load_library()
     which = "policy" if policy else which
-    err = {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error)
+    err = (lib.swarm_critic_last_error if which == "critic" else
+           {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error))
     msg = (err() or b"").decode(errors="replace")
     if rc in (SWARM_EINVAL, SWARM_ENULL, SWARM_ELIMIT):
         raise ValueError(f"swarm_mi355x error {rc}: {msg}")
