@@ -376,6 +376,92 @@ int swarm_gae(const float* reward, const float* value, const uint8_t* terminated
               float* advantage, float* value_target, void* hip_stream);
 
 /*
+ * PPO loss head (csrc/swarm_ppo.hip): RLlib's PPOTorchPolicy.loss over a collected fragment, value
+ * and gradient in one pass.  Rows are grouped by env-row: an env-row is one (t, e) with its N
+ * consecutive agent rows (the collector's [T,E,N,...] flatten); values are per env-row.
+ * Both entry points are async on hip_stream, allocate nothing and do not synchronise; rows == 0
+ * is a no-op (nothing is written); errors via swarm_ppo_last_error.  Every sum over rows is a
+ * two-stage f64 reduction without atomics: per-block partials go to `workspace`
+ * (SWARM_PPO_WORKSPACE_BYTES of device memory, 8-B aligned, private to the launch while it runs),
+ * and a one-wave finalising launch adds them in index order, in groups of 16 (lane j adds
+ * partials 16j .. 16j+15 in order, lane 0 then adds the 64 group sums in order).  The grid depends
+ * on `rows` (and N) only, so a launch repeats bit for bit.
+ */
+#define SWARM_PPO_MAX_ACT 6                 /* action dims A: logits are 2A <= SWARM_POLICY_MAX_OUT wide */
+#define SWARM_PPO_MAX_AGENTS 256            /* agents N of an env-row */
+#define SWARM_PPO_MAX_BLOCKS 1024           /* workgroups of a launch = partials of a sum */
+#define SWARM_PPO_WORKSPACE_BYTES 65536     /* SWARM_PPO_MAX_BLOCKS x 8 doubles */
+#define SWARM_PPO_MOMENTS 4                 /* doubles of a swarm_masked_moments result */
+#define SWARM_PPO_STATS 7                   /* doubles of swarm_ppo_loss's stats */
+
+/*
+ * RLlib's standardized(): over the rows with valid != 0,
+ *     out[0] = count,  out[1] = mean,  out[2] = population std (ddof 0),  out[3] = 1 / max(std, 1e-4)
+ * as four doubles on the device.  With count 0: mean 0, std 0 and out[3] = 1e4.  x of a row with
+ * valid == 0 is never used (it may be NaN).  Arithmetic, all f64:
+ *     thread:  p = its first valid x;  n, s = sum(x - p), q = sum((x - p)^2) over its valid rows
+ *     block :  nb = sum n,  mb = sum(n p + s) / nb,  M2b = sum(q - 2 (mb - p) s + n (mb - p)^2)
+ *              (fixed-shape tree: __shfl_down 32..1 in a wave, then the 4 wave sums in order)
+ *     final :  count = sum nb,  mean = sum(nb mb) / count,
+ *              std = sqrt(sum(M2b + nb (mb - mean)^2) / count)        (sums in index order, above)
+ */
+int swarm_masked_moments(const float* x, const uint8_t* valid, long long rows, void* workspace, double* out,
+                         void* hip_stream);
+
+typedef struct swarm_ppo_args {
+  const float* logits;         /* [R,2A] new policy [mean | log_std]; 8-B aligned */
+  const float* behaviour_logits; /* [R,2A] the policy that acted; 8-B aligned */
+  const float* actions;        /* [R,A]  */
+  const float* logp;           /* [R]    behaviour log-prob of the action */
+  const float* advantage;      /* [R]    raw (not standardised) */
+  const float* value_target;   /* [R]    */
+  const float* value;          /* [R/N]  new value of the env-row */
+  const uint8_t* valid;        /* [R]    */
+  const double* adv_moments;   /* swarm_masked_moments result used to standardise the advantages */
+  const double* valid_moments; /* swarm_masked_moments result over these R rows: [0] is M */
+  float* grad_logits;          /* [R,2A] d total / d logits; exactly 0 on invalid rows; 8-B aligned */
+  float* grad_value;           /* [R/N]  d total / d value */
+  double* stats;               /* [SWARM_PPO_STATS] */
+  void* workspace;             /* SWARM_PPO_WORKSPACE_BYTES */
+  long long rows;              /* R, a multiple of num_agents */
+  int32_t num_agents;          /* N in [1, SWARM_PPO_MAX_AGENTS] */
+  int32_t act_dim;             /* A in [1, SWARM_PPO_MAX_ACT] */
+  float clip_param, vf_clip_param, vf_loss_coeff, entropy_coeff, kl_coeff;
+} swarm_ppo_args_t;
+
+/*
+ * Per row with valid != 0 (nothing but the valid byte is read from any other row), in f32 without
+ * fused multiply-add, k over the A action dims, (mu, s) = logits, (mu0, s0) = behaviour_logits,
+ * v = value[row / N], c = clip_param:
+ *     adv  = (advantage - (float)adv_moments[1]) * (float)adv_moments[3]
+ *     e_k  = exp(-s_k);  z_k = (a_k - mu_k) e_k
+ *     lp   = sum_k(-0.5 z_k^2 - s_k) - 0.5 A log(2 pi)             (swarm_gaussian_logp's expression)
+ *     r    = exp(lp - logp)
+ *     surr = min(adv r, adv clamp(r, 1 - c, 1 + c))
+ *     clipped = (adv > 0 and r > 1 + c) or (adv < 0 and r < 1 - c)
+ *     d    = v - value_target;  vf = min(d^2, vf_clip_param)
+ *     H    = sum_k s_k + 0.5 A log(2 pi e)
+ *     u_k  = exp(2 s0_k) + (mu0_k - mu_k)^2
+ *     KL   = sum_k(s_k - s0_k + 0.5 u_k e_k^2 - 0.5)                (KL(behaviour || new))
+ *     loss = -surr + vf_loss_coeff vf - entropy_coeff H + kl_coeff KL
+ * and with M = valid_moments[0], inv = M > 0 ? 1 / M : 0, w = clipped ? 0 : -adv r:
+ *     grad_logits[row, k]     = inv (w z_k e_k + kl_coeff (mu_k - mu0_k) e_k^2)
+ *     grad_logits[row, A + k] = inv (w (z_k^2 - 1) - entropy_coeff + kl_coeff (1 - u_k e_k^2))
+ *     g_row = d^2 < vf_clip_param ? inv vf_loss_coeff 2 d : 0
+ *     grad_value[env-row] = sum of g_row over its agents in index order, in groups of 16 (group
+ *         sums first, then the group sums in order; invalid agents add 0; no atomics), so an
+ *         env-row without a valid agent gets 0
+ * grad_logits of a row with valid == 0 is 0.  stats (f64 sums of the f32 row terms, reduced like
+ * the moments: per-thread sums in row order, the block tree, the finalising launch):
+ *     [0] rows with valid != 0 (counted here)   [1] total = [2] + vf_loss_coeff [3] - entropy_coeff [4] + kl_coeff [5]
+ *     [2] inv sum(-surr)   [3] inv sum vf   [4] inv sum H   [5] inv sum KL   [6] inv sum clipped
+ * With M == 0 every gradient and stats [1..6] are 0.
+ */
+int swarm_ppo_loss(const swarm_ppo_args_t* args, void* hip_stream);
+
+const char* swarm_ppo_last_error(void);
+
+/*
  * On-device evaluation metrics: the per-episode summary of
  * scripts/evaluate_protocol.py:237-331 (`_run_single_episode_multi_agent`; formation error
  * :103-116) accumulated on the device from a step's outputs (obs, reward, info_flags, env_done:

@@ -59,6 +59,11 @@ EVAL_COLLIDED = 2
 EVAL_STEP_FUSED = 1
 EVAL_RECORD = 9
 EVAL_SEGMENTS = 64
+PPO_MAX_ACT = 6
+PPO_MAX_AGENTS = 256
+PPO_WORKSPACE_BYTES = 65536
+PPO_MOMENTS = 4
+PPO_STATS = 7
 
 # every symbol include/swarm_mi355x.h declares
 EXPORTED_SYMBOLS = (
@@ -69,9 +74,12 @@ EXPORTED_SYMBOLS = (
     "swarm_env_cfg_set",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
+    "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
 )
-# the rollout half (csrc/swarm_critic.hip); a diagnostic build given by path may leave the unit out
-ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-6:]
+# the rollout half (csrc/swarm_critic.hip) and the PPO loss head (csrc/swarm_ppo.hip); a diagnostic
+# build given by path may leave either unit out
+ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-9:-3]
+PPO_SYMBOLS = EXPORTED_SYMBOLS[-3:]
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -153,6 +161,15 @@ class SwarmPolicy(ctypes.Structure):
 
 class SwarmCritic(ctypes.Structure):
     _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
+class SwarmPpoArgs(ctypes.Structure):
+    """swarm_ppo_args_t."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("logits", "behaviour_logits", "actions", "logp", "advantage", "value_target", "value", "valid",
+                 "adv_moments", "valid_moments", "grad_logits", "grad_value", "stats", "workspace")] + [
+        ("rows", ctypes.c_longlong), ("num_agents", ctypes.c_int32), ("act_dim", ctypes.c_int32)] + [
+        (name, ctypes.c_float) for name in ("clip_param", "vf_clip_param", "vf_loss_coeff", "entropy_coeff", "kl_coeff")]
 
 
 class SwarmEval(ctypes.Structure):
@@ -242,6 +259,13 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.swarm_gae.restype = ctypes.c_int
         lib.swarm_gae.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_float, ctypes.c_float, vp, vp, vp]
+    if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
+        lib.swarm_masked_moments.restype = ctypes.c_int
+        lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
+        lib.swarm_ppo_loss.restype = ctypes.c_int
+        lib.swarm_ppo_loss.argtypes = [ctypes.POINTER(SwarmPpoArgs), vp]
+        lib.swarm_ppo_last_error.restype = ctypes.c_char_p
+        lib.swarm_ppo_last_error.argtypes = []
     got = lib.swarm_abi_version()
     if got != ABI_VERSION:
         raise NativeLibraryError(f"{p}: ABI version {got}, expected {ABI_VERSION}")
@@ -252,12 +276,12 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 
 def check(rc: int, lib: ctypes.CDLL | None = None, policy: bool = False, which: str | None = None) -> None:
     """Raise on a negative return code (bad arguments -> ValueError, HIP errors -> RuntimeError).
-    `which` names the component whose last-error string explains it ("policy", "eval", "critic")."""
+    `which` names the component whose last-error string explains it ("policy", "eval", "critic", "ppo")."""
     if rc == SWARM_OK:
         return
     lib = lib or load_library()
     which = "policy" if policy else which
-    err = (lib.swarm_critic_last_error if which == "critic" else
+    err = (lib.swarm_critic_last_error if which == "critic" else lib.swarm_ppo_last_error if which == "ppo" else
            {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error))
     msg = (err() or b"").decode(errors="replace")
     if rc in (SWARM_EINVAL, SWARM_ENULL, SWARM_ELIMIT):

@@ -93,6 +93,18 @@ class CriticMLP:
             raise ValueError(f"no in -> {h} -> {h} -> 1 dense chain under {prefix!r}: found {shapes}")
         return cls([(d[1], d[2]) for d in (rest[0], rest[1], last[0])], **kw)
 
+    def load_layers(self, layers) -> None:
+        """Replace the weights in place: `layers` = three (w, b) of the shapes this critic was built
+        with, re-packed and copied into the existing device blob on the current stream — the handle
+        and `weights.data_ptr()` stay valid."""
+        new = [(_np(w), _np(b).reshape(-1)) for w, b in layers]
+        if len(new) != 3 or any(w.shape != ow.shape or b.shape != ob.shape for (w, b), (ow, ob) in zip(new, self.layers)):
+            raise ValueError(f"expected 3 layers of the shapes {[w.shape for w, _ in self.layers]}")
+        nat.check(self.lib.swarm_critic_pack(self.in_dim, _PRECISION[self.precision], *map(_fp, (a for wb in new for a in wb)),
+                                             self.packed_host.ctypes.data_as(ctypes.c_void_p)), self.lib, which="critic")
+        self.weights.copy_(torch.from_numpy(self.packed_host))
+        self.layers = new
+
     # ------------------------------------------------------------------ forward
     def _check_gs(self, gs: torch.Tensor) -> int:
         if not isinstance(gs, torch.Tensor) or gs.device != self.device or gs.dtype != torch.float32:

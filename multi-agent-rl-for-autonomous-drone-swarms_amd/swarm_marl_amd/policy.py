@@ -71,6 +71,19 @@ class PolicyMLP:
     def from_arrays(cls, w1, b1, w2, b2, w3, b3, **kw) -> "PolicyMLP":
         return cls([(w1, b1, True), (w2, b2, True), (w3, b3, False)], **kw)
 
+    def load_layers(self, layers) -> None:
+        """Replace the weights in place: `layers` = three (w, b[, relu]) of the shapes this policy was
+        built with, re-packed and copied into the existing device blob on the current stream — the
+        handle and `weights.data_ptr()` stay valid."""
+        arrs = [np.ascontiguousarray(a, np.float32) for layer in layers for a in (layer[0], np.reshape(layer[1], -1))]
+        if len(layers) != 3 or any(a.shape != np.shape(old) for a, old in
+                                   zip(arrs, (x for wb in self.layers for x in (wb[0], np.reshape(wb[1], -1))))):
+            raise ValueError(f"expected 3 layers of the shapes {[w.shape for w, _ in self.layers]}")
+        nat.check(self.lib.swarm_policy_pack(self.in_dim, self.out_dim, _PRECISION[self.precision], *map(_fp, arrs),
+                                             self.packed_host.ctypes.data_as(ctypes.c_void_p)), self.lib, policy=True)
+        self.weights.copy_(torch.from_numpy(self.packed_host))
+        self.layers = [(arrs[2 * i].copy(), arrs[2 * i + 1].copy()) for i in range(3)]
+
     # ------------------------------------------------------------------ forward
     def _check_obs(self, obs: torch.Tensor) -> int:
         if not isinstance(obs, torch.Tensor) or obs.device != self.device or obs.dtype != torch.float32:
