@@ -529,6 +529,7 @@ int swarm_critic_forward(const swarm_critic_t* c, const float* gs, long long row
   a.rows = rows;
   a.in = c->in_dim;
   hipStream_t s = (hipStream_t)hip_stream;
+  // the per-CU caps (16 and 32 tiles) are mirrored by tests/test_gpu_critic.py test_second_grid_pass
   if (c->precision == SWARM_POLICY_BF16)
     hipLaunchKernelGGL(critic_mlp_bf16, dim3(grid_for((rows + TILE - 1) / TILE, 16)), dim3(BF16_THREADS), 0, s, a);
   else
@@ -541,6 +542,7 @@ int swarm_gaussian_logp(const float* logits, const float* actions, long long row
   if (rows < 0 || adim < 1) return cfail(SWARM_EINVAL, "rows < 0 or adim < 1");
   if (rows == 0) return SWARM_OK;
   if (!logits || !actions || !logp) return cfail(SWARM_ENULL, "logits/actions/logp is NULL");
+  // the per-CU cap (32 blocks, here and in swarm_gae) is mirrored by tests/test_gpu_rollout.py
   hipLaunchKernelGGL(gaussian_logp_kernel, dim3(grid_for((rows + 255) / 256, 32)), dim3(256), 0, (hipStream_t)hip_stream,
                      logits, actions, rows, adim, logp);
   return launch_status();

@@ -14,7 +14,11 @@ import ctypes
 import numpy as np
 import torch
 
-IN_DIMS = (15, 16, 21, 387, 1539)  # in_dim + 1 on / just over / just under a multiple of 16; N = 64; N = 256
+# in_dim + 1 on / just over / just under a multiple of 16; N = 64; N = 256 (nc1 = ceil((in + 1) / 32) W1
+# chunks: 1, 1, 1, 13, 49, all odd); then the minimum, in + 1 on / just over / just under 32 and 64, in
+# on 64 and 128 (the f32 kernel's 64-term blocks), N = 8 and N = 16: nc1 = 1, 1, 2, 2, 2, 3, 4, 5 (with
+# an even nc1 the first W2 chunk and a tile's last chunk sit in the other LDS buffer)
+IN_DIMS = (15, 16, 21, 387, 1539, 1, 31, 32, 51, 63, 64, 99, 128)
 H = 256
 
 

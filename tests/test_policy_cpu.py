@@ -364,3 +364,22 @@ def test_pack_f32x3_split_and_emulation_meet_the_f32_tolerance():
     got = emulate_x3_kernel(buf, obs, 6)
     ref = d["logits"][::3]
     assert np.all(np.abs(got - ref) <= 1e-4 + 1e-5 * np.abs(ref)), np.abs(got - ref).max()
+
+
+@pytest.mark.parametrize("shape", [(1, 2), (16, 4), (31, 12), (47, 12), (3, 6)])
+def test_emulations_are_generic_in_dims(shape):
+    """emulate_bf16_kernel / emulate_x3_kernel read d and out from their arguments: off the default
+    37 -> 6 (tests/policy_ref.py shapes; the GPU tests hold the kernels to them there) both still
+    compute the MLP — the x3 emulation within the f32 tolerance of float64, the bf16 one within
+    bf16's operand rounding of it."""
+    from swarm_marl_amd import _native as nat
+    from tests import policy_ref as pr
+    lib = nat.load_library()
+    layers = pr.make_actor(*shape)
+    x = pr.obs_set(shape[0])[:65]
+    ref = pr.forward64(layers, x)
+    x3 = emulate_x3_kernel(_pack(lib, layers, nat.POLICY_F32X3), x, shape[1])
+    assert x3.shape == ref.shape and np.all(np.abs(x3 - ref) <= 1e-4 + 1e-5 * np.abs(ref)), np.abs(x3 - ref).max()
+    emu = emulate_bf16_kernel(_pack(lib, layers, nat.POLICY_BF16), x, shape[1])
+    assert emu.shape == ref.shape and np.abs(emu - ref).max() < 0.05 * max(1.0, np.abs(ref).max())
+    assert np.abs(emu - ref).max() > 1e-6  # it is the rounded arithmetic, not the float64 forward again
