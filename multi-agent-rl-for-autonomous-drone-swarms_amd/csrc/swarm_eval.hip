@@ -142,6 +142,8 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_begin_kernel
 // the goal columns of a restarting one): the kernel is latency-bound (all 8192 waves of the
 // headline batch are resident at once), so the chain of dependent memory round trips, not the
 // bytes, sets its time.  A restart writes the new episode's start rows in the same pass.
+// Never launched for a SWARM_EVAL_STEP_FUSED tracker: the step kernel did the whole update
+// (swarm_kernel.hip s64_env) and swarm_eval_update returns before the launch.
 __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kernel(const EvalArgs a) {
   // agents with an observation this step (x, y, z, has); N float4 of dynamic LDS, so that the
   // LDS of a small swarm does not cap the waves per CU (a static EVAL_MAX_N array did: 16 KB)
@@ -161,10 +163,6 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
   if (!(status & SWARM_EVAL_LIVE)) return;
   const bool ends = (done & (SWARM_ENV_TERMINATED | SWARM_ENV_TRUNCATED)) != 0;
   const bool restarts = ends && (done & SWARM_ENV_RESET) != 0;
-  // SWARM_EVAL_STEP_FUSED: the step launch (out.eval) already added this step's reward, steps,
-  // reached step, collision vote and path lengths (swarm_kernel.hip s64_env, the same arithmetic):
-  // only the formation error and the episode ends are left here
-  const bool fused = (v.flags & SWARM_EVAL_STEP_FUSED) != 0;
   // ---- per-agent votes, path length, observed positions; path efficiency and the next
   // episode's start rows when the episode ends here
   double rsum = 0.0, pe = 0.0;
@@ -174,25 +172,6 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
     const uint8_t fl = a.info_flags[r];
     float ox, oy, oz;
     obs_pos(a, r, ox, oy, oz);
-    if (fused) {  // observed positions for the formation error; the ended episode's path efficiency
-      const bool has = (fl & SWARM_AGENT_HAS_OBS) != 0;
-      n_obs += has ? 1 : 0;
-      pos[i] = has ? make_float4(ox, oy, oz, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ends) {
-        const double tr = v.traveled[r];
-        const float straight = norm1d(v.start[3 * r] - v.goal[3 * r], v.start[3 * r + 1] - v.goal[3 * r + 1],
-                                      v.start[3 * r + 2] - v.goal[3 * r + 2]);
-        pe += tr > 1e-8 ? (double)straight / tr : 0.0;
-      }
-      if (restarts) {
-        float rx, ry, rz;
-        obs_goal_vec(a, e, r, ox, oy, oz, rx, ry, rz);
-        v.start[3 * r] = ox; v.start[3 * r + 1] = oy; v.start[3 * r + 2] = oz;
-        v.goal[3 * r] = ox + rx; v.goal[3 * r + 1] = oy + ry; v.goal[3 * r + 2] = oz + rz;
-        v.traveled[r] = 0.0;
-      }
-      continue;
-    }
     const float rw = a.reward[r];
     const float lx = v.last[3 * r], ly = v.last[3 * r + 1], lz = v.last[3 * r + 2];
     double tr = v.traveled[r];
@@ -309,14 +288,13 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
   }
   if (ends) pe = wave_sum(pe) / (double)a.N;
   if (t != 0) return;
-  const double ep_reward = fused ? ep_reward0 : ep_reward0 + (n_st > 0 ? rsum / (double)n_st : 0.0);
+  const double ep_reward = ep_reward0 + (n_st > 0 ? rsum / (double)n_st : 0.0);
   const double fe_sum = fe_sum0 + fe;
-  const int steps = fused ? steps0 : steps0 + 1;
+  const int steps = steps0 + 1;
   int reached = reached0;
-  if (!fused && !not_reached && reached < 0) reached = steps;
+  if (!not_reached && reached < 0) reached = steps;
   if (!ends) {
     v.fe_sum[e] = fe_sum;
-    if (fused) return;
     v.ep_reward[e] = ep_reward;
     v.ep_steps[e] = steps;
     v.reached_step[e] = reached;

@@ -63,6 +63,125 @@ def test_eval_oracle_matches_reference(name):
         assert (isinstance(v, float) and math.isnan(v) and math.isnan(agg[key])) or agg[key] == pytest.approx(v, rel=1e-12), key
 
 
+# ---------------------------------------------------------------- the dense reference (tests/eval_ref.py)
+def _same(a, b, rel=1e-12):
+    return (math.isnan(a) and math.isnan(b)) or a == pytest.approx(b, rel=rel, abs=1e-12)
+
+
+def _dense_from_dicts(ids, out, d_obs):
+    """One env's step dicts (obs, rew, term, trunc, infos) as the dense arrays of E = 1."""
+    from tests import eval_ref as er
+    obs_d, rew_d, term, trunc, infos = out
+    n = len(ids)
+    obs = np.zeros((1, n, d_obs), np.float32)
+    rew = np.zeros((1, n), np.float64)
+    fl = np.zeros((1, n), np.uint8)
+    for i, a in enumerate(ids):
+        if a in rew_d:
+            fl[0, i] |= er.STEPPED
+            rew[0, i] = rew_d[a]
+        if a in obs_d:
+            obs[0, i] = obs_d[a]
+            fl[0, i] |= er.HAS_OBS
+            fl[0, i] |= er.REACHED if infos[a]["reached_goal"] else 0
+            fl[0, i] |= er.COLLISION if infos[a]["collision"] else 0
+    done = np.array([(er.TERMINATED if term["__all__"] else 0) | (er.TRUNCATED if trunc["__all__"] else 0)], np.uint8)
+    return obs, rew, fl, done
+
+
+def test_dense_distance_is_the_oracles():
+    """eval_ref.distance == float(np.linalg.norm(a - b)) of float32 vectors, bit for bit, also for
+    separations far below the float32 normal range of the square."""
+    from oracle import eval_oracle as ev
+    from tests import eval_ref as er
+    rng = np.random.default_rng(3)
+    a = rng.uniform(-10, 10, (400, 3)).astype(np.float32)
+    b = rng.uniform(-10, 10, (400, 3)).astype(np.float32)
+    b[:40] = a[:40] + (rng.uniform(-1, 1, (40, 3)) * 2.0 ** rng.integers(-70, -20, (40, 1))).astype(np.float32)
+    got, _ = er.distance(a, b)
+    assert got.dtype == np.float32
+    assert [float(x) for x in got] == [ev.distance(a[i], b[i]) for i in range(len(a))]
+
+
+@pytest.mark.parametrize("name", EVAL_FIXTURES)
+def test_dense_reference_matches_reference_fixtures(name):
+    """tests/eval_ref.DenseEvalRef reproduces every EpisodeSummary of the reference-made fixtures
+    and their aggregate, as the oracle does (test_eval_oracle_matches_reference)."""
+    from oracle import eval_oracle as ev
+    from tests import eval_ref as er
+    d = np.load(GOLDEN / name)
+    cfg = json.loads(str(d["config"]))
+    spacing = float(cfg.get("desired_spacing", 2.5))
+    sums = []
+    for k in range(len(d["lengths"])):
+        reset_obs, outs = replay_episode(d, cfg, k)
+        ids = list(reset_obs)
+        obs0 = np.stack([reset_obs[a] for a in ids])[None]
+        ref = er.DenseEvalRef(1, len(ids), spacing)
+        ref.begin(obs0)
+        for o in outs:
+            ref.update(*_dense_from_dicts(ids, o, obs0.shape[-1]))
+        rec = ref.records()
+        assert len(rec) == 1 and int(rec[0, 7]) == int(d["lengths"][k]) and not ref.live.any()
+        s = tuple(float(x) for x in rec[0, 1:7])
+        for f, (a, b) in enumerate(zip(s, d["summaries"][k])):
+            assert _same(a, b), (name, k, f)
+        sums.append(s)
+    agg = ev.aggregate(sums)
+    for key, v in json.loads(str(d["aggregate"])).items():
+        assert (isinstance(v, float) and math.isnan(v) and math.isnan(agg[key])) or agg[key] == pytest.approx(v, rel=1e-12), key
+
+
+@pytest.mark.parametrize("point", ["reach", "full", "collide"])
+@pytest.mark.parametrize("n", [2, 17, 64, 65])
+def test_dense_reference_matches_oracle_rollout(n, point):
+    """The dense reference against oracle/eval_oracle.EpisodeMetrics on an auto-reset rollout of
+    oracle/swarm_oracle (E = 4, 30 steps, the eval tests' parameter points and action rule):
+    discrete fields, steps and update index exact, formation error / path efficiency / episode
+    reward to 1e-12 relative; and the step / episode classes each point is there for occur."""
+    from oracle import eval_oracle as ev_o
+    from swarm_marl_amd.envs.drone_swarm_env import build_step_dicts
+    from tests import eval_ref as er
+    e, steps = 4, 30
+    ids = [f"drone_{i}" for i in range(n)]
+
+    def reset_obs(o, i):
+        return {a: o[i, k].copy() for k, a in enumerate(ids)}
+
+    it = er.oracle_rollout(er.point_cfg(point, n), e, steps, seed=5, noise_seed=11)
+    obs = next(it)
+    ref = er.DenseEvalRef(e, n, 2.5)
+    ref.begin(obs)
+    trackers = [ev_o.EpisodeMetrics(reset_obs(obs, i), 2.5) for i in range(e)]
+    expected = []
+    for t, (obs, rew, fl, done, out) in enumerate(it):
+        ref.update(obs, rew, fl, done)
+        for i in range(e):
+            outs = build_step_dicts(ids, obs[i], rew[i], out["terminated"][i], out["truncated"][i], fl[i],
+                                    out["dist_goal"][i], None, int(done[i]), gs_info={})
+            if trackers[i].update(*outs):
+                expected.append((t + 1, i, trackers[i].summary(), trackers[i].steps))
+                assert done[i] & er.RESET
+                trackers[i] = ev_o.EpisodeMetrics(reset_obs(obs, i), 2.5)
+    rec = ref.records()
+    assert len(rec) == len(expected) > 0
+    for row, (upd, i, s, st) in zip(rec, sorted(expected, key=lambda x: (x[0], x[1]))):
+        assert int(row[0]) == i and int(row[8]) == upd and int(row[7]) == st
+        assert row[1] == s[0] and row[2] == s[1] and ((math.isnan(row[3]) and math.isnan(s[2])) or row[3] == s[2])
+        for f in (3, 4, 5):
+            assert _same(float(row[1 + f]), s[f]), (n, point, i, f)
+    c = ref.counts
+    assert c["zero"] == len(rec) and c["restarts"] == len(rec)  # every end is a terminal step and restarts
+    if point == "reach":  # shrinking observed sets down to one drone, all-reached ends
+        assert c["one"] > 0 and c["end_all_reached"] > 0
+        assert (c["two"] > 0 and c["partial"] > 0) if n >= 4 else c["full"] > 0
+    elif point == "full":  # fully observed steps, time-limit ends
+        assert c["full"] > 0 and c["end_time_limit"] > 0
+        assert c["partial"] > 0 or n < 64
+    elif n >= 17:  # two drones rarely meet
+        assert c["end_collision"] > 0
+
+
 EVAL1_FIXTURES = sorted(p.name for p in GOLDEN.glob("eval1_*.npz"))
 
 

@@ -76,7 +76,7 @@ def test_eval_replays_reference_episodes(dev, name):
 def test_eval_auto_reset_matches_oracle(dev, n):
     """The unfused update kernel (not N = 64) against the oracle's episode metrics with
     auto-reset: N = 8 / 16 take the small-swarm formation path (several lanes per drone), N = 33 /
-    40 the general symmetric-rotation one (odd N, and even N with its opposite pairs)."""
+    40 the serial general loop (one drone per lane, every partner in turn; odd and even N)."""
     from oracle import eval_oracle as ev_o
     from swarm_marl_amd import VecSwarm
     from swarm_marl_amd import _native as nat
@@ -146,8 +146,8 @@ def _run_tracker(dev, fused, groups, native_groups=False, e=64, steps=70):
 
 @pytest.mark.parametrize("groups,native", [(1, False), (2, False), (2, True), (3, True)])
 def test_fused_eval_equals_unfused(dev, groups, native):
-    """SWARM_EVAL_STEP_FUSED (the step accumulates reward / steps / votes / path length in its
-    write-back, swarm_eval_update only the formation error): the same records, bit for bit, as
+    """SWARM_EVAL_STEP_FUSED (the step does the whole update in its write-back, formation error and
+    records included; swarm_eval_update launches nothing): the same records, bit for bit, as
     the unfused update at the headline shape (N = 64, swarm_step64_once), with env groups too."""
     a = _run_tracker(dev, True, groups, native)
     b = _run_tracker(dev, False, 1)
