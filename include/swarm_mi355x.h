@@ -318,6 +318,84 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
 const char* swarm_policy_last_error(void);
 
 /*
+ * On-device attention actor: the reference's CentralizedCriticModel(use_attention=True) actor
+ * (src/swarm_marl/training/models.py:104-137, scripts/train_attention.py), eval mode.  For one
+ * observation row x of width D = 9 + 4K + 4Ms, own = x[0:9], nb_j = x[9+4j : 13+4j] (j < K),
+ * obst = x[9+4K : D]:
+ *     o   = relu(W_own own + b_own)                     (32)   own_embed.0
+ *     e_j = relu(W_nb nb_j + b_nb)                      (32)   neighbor_embed.0
+ *     q = Wq o + bq,  k_j = Wk e_j + bk,  v_j = Wv e_j + bv    in_proj rows 0:32, 32:64, 64:96
+ *     a = softmax_j(q . k_j / sqrt(32)),  c = Wout (sum_j a_j v_j) + bout
+ *     logits = W3 relu(W2 relu(W1 [own | c | obst] + b1) + b2) + b3      (W1 [256, 41 + 4Ms])
+ * Every one of the K neighbour slots is attended to, a zero-filled one included.
+ * K in 1..SWARM_ATTN_MAX_K, Ms in 0..SWARM_ATTN_MAX_MS, out_dim even in 2..SWARM_POLICY_MAX_OUT;
+ * anything else is SWARM_ELIMIT.  precision: SWARM_POLICY_BF16 or SWARM_POLICY_F32
+ * (SWARM_POLICY_F32X3: SWARM_ELIMIT).
+ *
+ * SWARM_POLICY_F32 evaluates the formulas above as written (f32 products and sums).
+ * SWARM_POLICY_BF16 is one fused launch on two exact identities, folded by the packer in double:
+ *     score_j = (A o + c0) . e_j + (terms equal for every j),  A = Wk^T Wq / sqrt(32),
+ *                                                              c0 = Wk^T bq / sqrt(32)
+ *     W1[:, 9:41] c = F s + d,   s = sum_j a_j e_j,   F = W1[:, 9:41] Wout Wv,
+ *                                                     d = W1[:, 9:41] (Wout bv + bout)
+ * The front end (o, A o + c0, e_j, the softmax with the running row maximum subtracted, s) runs in f32; the
+ * trunk runs on v_mfma_f32_32x32x16_bf16 with f32 accumulation over the 64-wide layer-1 input
+ * [s (32) | own (9) | obst (4Ms) | 1 | 0...], whose weights [F | W1[:, 0:9] | W1[:, 41:] | b1 + d]
+ * are rounded to bf16 once.
+ *
+ * bf16 blob layout (bytes; `out` = out_dim): W2 fragments at 0 (131072), W3 fragments (512 out),
+ * b2 (1024), b3 (128), layer-1 fragments (32768), then the f32 front end: W_own [32,9], b_own [32],
+ * W_nb [32,4], b_nb [32], A [32,32] (row i, column m: t_i = c0_i + sum_m A[i][m] o_m), c0 [32].
+ * Fragment order is swarm_policy_pack's; layer-1 fragment column k < 32 carries
+ * s[16 ((k >> 3) & 1) + 8 (k >> 4) + (k & 7)], column 32 + t the t-th of [own | obst | 1].
+ */
+#define SWARM_ATTN_EMBED 32         /* embed_dim of the reference's attention block (one head) */
+#define SWARM_ATTN_MAX_K 16         /* neighbour slots */
+#define SWARM_ATTN_MAX_MS 5         /* sensed obstacles: 41 + 4 Ms + the bias column fit a 64-wide K */
+
+typedef struct swarm_attn_policy {
+  int32_t neighbor_k;        /* K */
+  int32_t sensed_obstacles;  /* Ms */
+  int32_t out_dim;           /* logits width (even) */
+  int32_t precision;         /* SWARM_POLICY_BF16 / SWARM_POLICY_F32 */
+  const void* weights;       /* device copy of the swarm_attn_policy_pack blob (16-B aligned) */
+} swarm_attn_policy_t;
+
+/* Row-major f32 parameters (PyTorch layouts), named after the reference's state_dict. */
+typedef struct swarm_attn_weights {
+  const float* neighbor_w;   /* neighbor_embed.0.weight [32,4] */
+  const float* neighbor_b;   /* neighbor_embed.0.bias [32] */
+  const float* own_w;        /* own_embed.0.weight [32,9] */
+  const float* own_b;        /* own_embed.0.bias [32] */
+  const float* in_proj_w;    /* attn_block.attn.in_proj_weight [96,32] */
+  const float* in_proj_b;    /* attn_block.attn.in_proj_bias [96] */
+  const float* out_proj_w;   /* attn_block.attn.out_proj.weight [32,32] */
+  const float* out_proj_b;   /* attn_block.attn.out_proj.bias [32] */
+  const float* w1;           /* trunk [256, 41 + 4Ms] */
+  const float* b1;
+  const float* w2;           /* [256,256] */
+  const float* b2;
+  const float* w3;           /* [out,256] */
+  const float* b3;
+} swarm_attn_weights_t;
+
+/* Bytes of the packed weight blob (negative SWARM_E* code for unsupported dims). */
+long long swarm_attn_policy_packed_bytes(int neighbor_k, int sensed_obstacles, int out_dim, int precision);
+
+/* Fold (double) and pack the parameters into the kernel's blob at host_out (host memory). */
+int swarm_attn_policy_pack(int neighbor_k, int sensed_obstacles, int out_dim, int precision,
+                           const swarm_attn_weights_t* w, void* host_out);
+
+/* logits [rows,out] (nullable) and/or actions [rows,out/2] (nullable) for obs [rows,D]; async on
+ * hip_stream, no allocation, no sync.  rows == 0 is a no-op.  SWARM_POLICY_ACT_SAMPLE draws the
+ * normals of swarm_policy_forward at the same (seed, row, counter), in either precision. */
+int swarm_attn_policy_forward(const swarm_attn_policy_t* p, const float* obs, long long rows, float* logits,
+                              float* actions, int action_mode, unsigned long long seed, unsigned long long counter,
+                              void* hip_stream);
+
+const char* swarm_attn_policy_last_error(void);
+
+/*
  * On-device centralized critic (the reference's CTDE value function: CentralizedCriticModel's
  * `value_model`, a TorchFC [256, 256] on global_state of width G = 6N + 3 with one output;
  * src/swarm_marl/training/models.py):

@@ -53,6 +53,9 @@ POLICY_F32 = 1
 POLICY_F32X3 = 2
 POLICY_ACT_MEAN = 0
 POLICY_ACT_SAMPLE = 1
+ATTN_EMBED = 32
+ATTN_MAX_K = 16
+ATTN_MAX_MS = 5
 CRITIC_MAX_IN = 1539
 EVAL_LIVE = 1
 EVAL_COLLIDED = 2
@@ -70,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "swarm_abi_version", "swarm_last_error", "swarm_params_default", "swarm_obs_dim",
     "swarm_query_launch", "swarm_step", "swarm_step_groups", "swarm_reset", "swarm_observe",
     "swarm_policy_packed_bytes", "swarm_policy_pack", "swarm_policy_forward", "swarm_policy_last_error",
+    "swarm_attn_policy_packed_bytes", "swarm_attn_policy_pack", "swarm_attn_policy_forward",
+    "swarm_attn_policy_last_error",
     "swarm_eval_begin", "swarm_eval_update", "swarm_eval_single_update", "swarm_eval_last_error",
     "swarm_env_cfg_set",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
@@ -80,6 +85,7 @@ EXPORTED_SYMBOLS = (
 # build given by path may leave either unit out
 ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-9:-3]
 PPO_SYMBOLS = EXPORTED_SYMBOLS[-3:]
+ATTN_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_attn_"))  # csrc/swarm_attn.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -159,6 +165,21 @@ class SwarmPolicy(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("weights", ctypes.c_void_p)]
 
 
+class SwarmAttnPolicy(ctypes.Structure):
+    """swarm_attn_policy_t."""
+    _fields_ = [("neighbor_k", ctypes.c_int32), ("sensed_obstacles", ctypes.c_int32), ("out_dim", ctypes.c_int32),
+                ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
+ATTN_WEIGHT_FIELDS = ("neighbor_w", "neighbor_b", "own_w", "own_b", "in_proj_w", "in_proj_b", "out_proj_w",
+                      "out_proj_b", "w1", "b1", "w2", "b2", "w3", "b3")
+
+
+class SwarmAttnWeights(ctypes.Structure):
+    """swarm_attn_weights_t: host pointers to the row-major f32 parameters."""
+    _fields_ = [(name, ctypes.POINTER(ctypes.c_float)) for name in ATTN_WEIGHT_FIELDS]
+
+
 class SwarmCritic(ctypes.Structure):
     _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
 
@@ -234,6 +255,17 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
                                          ctypes.c_ulonglong, ctypes.c_ulonglong, vp]
     lib.swarm_policy_last_error.restype = ctypes.c_char_p
     lib.swarm_policy_last_error.argtypes = []
+    if path is None or all(hasattr(lib, name) for name in ATTN_SYMBOLS):
+        lib.swarm_attn_policy_packed_bytes.restype = ctypes.c_longlong
+        lib.swarm_attn_policy_packed_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        lib.swarm_attn_policy_pack.restype = ctypes.c_int
+        lib.swarm_attn_policy_pack.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(SwarmAttnWeights), vp]
+        lib.swarm_attn_policy_forward.restype = ctypes.c_int
+        lib.swarm_attn_policy_forward.argtypes = [ctypes.POINTER(SwarmAttnPolicy), vp, ctypes.c_longlong, vp, vp,
+                                                  ctypes.c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, vp]
+        lib.swarm_attn_policy_last_error.restype = ctypes.c_char_p
+        lib.swarm_attn_policy_last_error.argtypes = []
     ev = ctypes.POINTER(SwarmEval)
     lib.swarm_eval_begin.restype = ctypes.c_int
     lib.swarm_eval_begin.argtypes = [P, ev, O, vp, vp]
@@ -276,12 +308,14 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 
 def check(rc: int, lib: ctypes.CDLL | None = None, policy: bool = False, which: str | None = None) -> None:
     """Raise on a negative return code (bad arguments -> ValueError, HIP errors -> RuntimeError).
-    `which` names the component whose last-error string explains it ("policy", "eval", "critic", "ppo")."""
+    `which` names the component whose last-error string explains it ("policy", "attn", "eval", "critic",
+    "ppo")."""
     if rc == SWARM_OK:
         return
     lib = lib or load_library()
     which = "policy" if policy else which
     err = (lib.swarm_critic_last_error if which == "critic" else lib.swarm_ppo_last_error if which == "ppo" else
+           lib.swarm_attn_policy_last_error if which == "attn" else
            {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error))
     msg = (err() or b"").decode(errors="replace")
     if rc in (SWARM_EINVAL, SWARM_ENULL, SWARM_ELIMIT):

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
 from .rollout import _F32, _U8, _check, _stream
@@ -158,7 +159,9 @@ class PPOLearner:
 
     The trainable copies are float32 torch MLPs (`actor`: D -> 256 -> 256 -> 2A, `value_net`:
     G -> 256 -> 256 -> 1, relu) initialised from `policy.layers` / `critic.layers`, under one
-    torch.optim.Adam.  `update(batch)`: the advantage moments once over the whole fragment; per
+    torch.optim.Adam.  With an `AttentionPolicy` the actor is an `AttentionActor` (the reference's
+    module on nn.MultiheadAttention, initialised from `policy.params` / `policy.layers`) under the same
+    Adam, written back with `load_params`.  `update(batch)`: the advantage moments once over the whole fragment; per
     epoch a seeded permutation of the env-rows; per minibatch of `minibatch_env_rows` env-rows an
     index_select gather into preallocated buffers, the valid count, both forwards, `ppo_loss`,
     backward and an Adam step; then RLlib's adaptive KL coefficient from the last epoch's mean KL
@@ -169,7 +172,7 @@ class PPOLearner:
 
     def __init__(self, policy: PolicyMLP, critic: CriticMLP, *, lr: float = 3e-4, num_epochs: int = 10,
                  minibatch_env_rows: int, kl_target: float = 0.01, seed: int = 0, **loss_kw):
-        if not isinstance(policy, PolicyMLP) or not isinstance(critic, CriticMLP):
+        if not isinstance(policy, (PolicyMLP, AttentionPolicy)) or not isinstance(critic, CriticMLP):
             raise ValueError("PPOLearner needs a PolicyMLP and a CriticMLP")
         if policy.device != critic.device:
             raise ValueError(f"policy is on {policy.device}, critic on {critic.device}")
@@ -185,7 +188,8 @@ class PPOLearner:
         self.kl_target = float(kl_target)
         self.kl_coeff = float(loss_kw.pop("kl_coeff", 0.2))
         self.loss_kw = loss_kw
-        self.actor = _mlp(policy.layers, self.device)
+        self.actor = (AttentionActor.from_policy(policy).to(self.device) if isinstance(policy, AttentionPolicy)
+                      else _mlp(policy.layers, self.device))
         self.value_net = _mlp(critic.layers, self.device)
         self.optimizer = torch.optim.Adam(list(self.actor.parameters()) + list(self.value_net.parameters()), lr=lr)
         self.generator = torch.Generator(device=self.device).manual_seed(int(seed))
@@ -256,6 +260,9 @@ class PPOLearner:
             self.kl_coeff *= 0.5
         info["kl_coeff"] = self.kl_coeff
         info["epoch_total_loss"] = [float(v) for v in host[:, 1]]
-        self.policy.load_layers(_layers_of(self.actor))
+        if isinstance(self.policy, AttentionPolicy):
+            self.policy.load_params(*self.actor.split_state())
+        else:
+            self.policy.load_layers(_layers_of(self.actor))
         self.critic.load_layers(_layers_of(self.value_net))
         return info

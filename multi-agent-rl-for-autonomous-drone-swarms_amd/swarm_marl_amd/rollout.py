@@ -1,6 +1,6 @@
 """PPO-ready rollout fragments collected on the device.
 
-`RolloutCollector` ties a `VecSwarm`, a `PolicyMLP` and (optionally) a `CriticMLP` together: T
+`RolloutCollector` ties a `VecSwarm`, a `PolicyMLP` or `AttentionPolicy` and (optionally) a `CriticMLP` together: T
 steps of policy + env step with every per-step quantity copied into preallocated [T, ...] buffers,
 then one critic launch over the (T+1) x E recorded global states, one log-prob launch and one GAE
 launch — no host synchronisation and no allocation after construction.
@@ -23,6 +23,7 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
+from .attention import AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
 from .vec_env import VecSwarm
@@ -94,7 +95,9 @@ def gae(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, tru
 
 
 class RolloutCollector:
-    """Collects fragments of `horizon` steps from `vec` under `policy`; see the module docstring.
+    """Collects fragments of `horizon` steps from `vec` under `policy` (a `PolicyMLP` or an
+    `AttentionPolicy`: anything with their in_dim / out_dim / device and forward); see the module
+    docstring.
 
     Buffers (attributes, and the dict `collect()` returns), G = 6N + 3:
       obs [T,E,N,D], logits [T,E,N,out], actions [T,E,N,out/2], logp / reward / advantage /
@@ -102,7 +105,7 @@ class RolloutCollector:
       global_state [T+1,E,G] and value [T+1,E] (row t: before step t; row T: after the last step).
     """
 
-    def __init__(self, vec: VecSwarm, policy: PolicyMLP, critic: CriticMLP | None = None, *, horizon: int,
+    def __init__(self, vec: VecSwarm, policy: PolicyMLP | AttentionPolicy, critic: CriticMLP | None = None, *, horizon: int,
                  gamma: float = 0.99, lam: float = 0.95, seed: int = 0):
         t = int(horizon)
         if t < 1:
