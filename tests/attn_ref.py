@@ -17,6 +17,10 @@ ROWS = 257
 # (K, Ms, out): the default; one neighbour (softmax over one slot); no obstacles and the narrowest
 # logits; every maximum (the 64-wide layer-1 K is full to column 61); a small odd-ish mix
 SHAPES = ((3, 4, 6), (1, 4, 6), (6, 0, 2), (16, 5, 12), (2, 1, 6))
+# the logits widths SHAPES leaves out (out = 4, 8, 10: ad = 2, 4, 5; at ad = 4 the log-std half sits
+# wholly in the other lane half, at ad = 5 it straddles it) with sensed_obstacles = 2 and 3.  Kept
+# apart so that SHAPES and the measured table of DESIGN.md §5.4 keep their meaning.
+MORE_SHAPES = ((5, 2, 4), (8, 3, 8), (11, 5, 10))
 ROW_COUNTS = (1, 33, 257)  # a lone row, one past a 32-row tile, one past a 256-row workgroup
 
 NAMES = ("neighbor_embed.0.weight", "neighbor_embed.0.bias", "own_embed.0.weight", "own_embed.0.bias",
@@ -26,11 +30,13 @@ _SHAPES = ((EM, 4), (EM,), (EM, 9), (EM,), (3 * EM, EM), (3 * EM,), (EM, EM), (E
 
 
 def make_attn(k: int, ms: int, out: int, *, log_std_scale: float | None = None, in_proj_scale: float = 1.0,
-              seed_offset: int = 0):
+              seed_offset: int = 0, q_scale: float = 1.0):
     """(params, layers): params maps the reference's names to float32 arrays, layers = [(w, b)] x 3 of
     the trunk (41 + 4 ms -> 256 -> 256 -> out).  Weights uniform(-1, 1) / sqrt(fan_in); biases
     uniform(-1, 1) / sqrt(fan_in) of their layer (small, non-zero).  `log_std_scale` as in
-    tests/policy_ref.py make_actor; `in_proj_scale` multiplies in_proj_weight (the peaked fixture)."""
+    tests/policy_ref.py make_actor; `in_proj_scale` multiplies in_proj_weight (the peaked fixture);
+    `q_scale` multiplies the query third of in_proj_weight and in_proj_bias only (rows [:32]): the
+    scores grow, Wv and with it the folded F = W1c Wout Wv keep their size (the saturated fixture)."""
     rng = np.random.default_rng(100000 * k + 1000 * ms + out + 7919 * seed_offset)
     params = {}
     for (wn, ws), (bn, bs) in zip(zip(NAMES[0::2], _SHAPES[0::2]), zip(NAMES[1::2], _SHAPES[1::2])):
@@ -39,6 +45,9 @@ def make_attn(k: int, ms: int, out: int, *, log_std_scale: float | None = None, 
         params[bn] = rng.uniform(-1, 1, bs).astype(np.float32) / fan
     params["attn_block.attn.in_proj_weight"] = (params["attn_block.attn.in_proj_weight"]
                                                 * np.float32(in_proj_scale)).astype(np.float32)
+    if q_scale != 1.0:
+        params["attn_block.attn.in_proj_weight"][:EM] *= np.float32(q_scale)
+        params["attn_block.attn.in_proj_bias"][:EM] *= np.float32(q_scale)
     in1 = 9 + EM + 4 * ms
     layers = []
     for shape in ((H, in1), (H, H), (out, H)):
@@ -154,3 +163,45 @@ def forward_bf16_emu(params, layers, k: int, ms: int, x: np.ndarray) -> np.ndarr
     h1 = bf16(np.maximum(xin @ w1.T, 0))
     h2 = bf16(np.maximum(h1 @ bf16(layers[1][0]).T + layers[1][1].astype(np.float64), 0))
     return h2 @ bf16(layers[2][0]).T + layers[2][1].astype(np.float64)
+
+
+# ---------------------------------------------------------------- the saturated softmax fixture
+SAT_SHAPE = (16, 5, 12)
+SAT_Q_SCALE = 144.0
+SAT_ROWS = 97          # one full 64-row group and a 33-row group
+SAT_SPAN = 104.0       # max score - min score: f32 exp(-104) is 0
+SAT_GAP = 30.0         # top score - second score: every other weight is below exp(-30) < 1e-13
+
+
+def make_saturated():
+    """(params, layers) of the saturated fixture: SAT_SHAPE, seed_offset 1, the query scaled by 144."""
+    return make_attn(*SAT_SHAPE, seed_offset=1, q_scale=SAT_Q_SCALE)
+
+
+def saturated_rows(params, layers, pool: int = 8192):
+    """(x, score): the first SAT_ROWS rows of obs_set(K, Ms, rows=pool) whose float64 scores span more
+    than SAT_SPAN with the top one more than SAT_GAP above the second, and those scores.  Fewer than
+    SAT_ROWS rows come back when the pool holds fewer (the caller asserts the count)."""
+    k, ms, _ = SAT_SHAPE
+    x = obs_set(k, ms, rows=pool)
+    _, score, _ = forward64(params, layers, k, x, details=True)
+    srt = np.sort(score, axis=1)
+    keep = (srt[:, -1] - srt[:, 0] > SAT_SPAN) & (srt[:, -1] - srt[:, -2] > SAT_GAP)
+    return x[keep][:SAT_ROWS], score[keep][:SAT_ROWS]
+
+
+def reorder_slots(x: np.ndarray, k: int, order: np.ndarray) -> np.ndarray:
+    """x with row r's neighbour slot j replaced by its slot order[r, j]; own and obstacle columns stay."""
+    out = x.copy()
+    nb = x[:, 9:9 + 4 * k].reshape(len(x), k, 4)
+    out[:, 9:9 + 4 * k] = np.take_along_axis(nb, order[:, :, None], axis=1).reshape(len(x), 4 * k)
+    return out
+
+
+def saturated_variants(params, layers, pool: int = 8192):
+    """{"drawn", "ascending", "descending"} -> observations [<= SAT_ROWS, D]: the selected rows as drawn,
+    and with the slots of every row permuted into ascending / descending float64 score."""
+    x, score = saturated_rows(params, layers, pool)
+    asc = np.argsort(score, axis=1, kind="stable")
+    return {"drawn": x, "ascending": reorder_slots(x, SAT_SHAPE[0], asc),
+            "descending": reorder_slots(x, SAT_SHAPE[0], asc[:, ::-1])}

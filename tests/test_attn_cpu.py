@@ -6,7 +6,10 @@ launched: the packer is host code, and every rejected call returns before touchi
   <= 1e-12 (both measured <= 5e-16);
 * the packer's folded matrices, read back from the bf16 blob, against the float64 folds rounded the
   way the header says (A, c0 to f32; the folded first layer to f32 then bf16): exact;
-* state_dict names, validation errors, the struct layouts against the header.
+* state_dict names, validation errors, the struct layouts against the header;
+* the premises of the GPU tests' fixtures: the saturated softmax fixture (its row count, score span
+  and gap, monotone slot orders, order-independent reference), `q_scale`, the log-std range of the
+  sampling fixtures at attn_ref.MORE_SHAPES.
 """
 from __future__ import annotations
 
@@ -65,7 +68,7 @@ class _TorchReference(torch.nn.Module):
         return self.fc[2](torch.relu(self.fc[1](torch.relu(self.fc[0](h)))))
 
 
-@pytest.mark.parametrize("k,ms,out", ar.SHAPES)
+@pytest.mark.parametrize("k,ms,out", ar.SHAPES + ar.MORE_SHAPES)
 def test_reference_matches_torch_float64(k, ms, out):
     from swarm_marl_amd import AttentionActor
     params, layers = ar.make_attn(k, ms, out)
@@ -104,7 +107,7 @@ def test_folds_are_exact_identities():
     assert np.abs(c @ w1c.T - (s @ f["F"].T + f["d"])).max() <= 1e-12
 
 
-@pytest.mark.parametrize("k,ms,out", ar.SHAPES)
+@pytest.mark.parametrize("k,ms,out", ar.SHAPES + ar.MORE_SHAPES)
 def test_packer_folds_match_float64(k, ms, out):
     from swarm_marl_amd.attention import AttentionPolicy, unpack_bf16_blob
     params, layers = ar.make_attn(k, ms, out)
@@ -128,6 +131,65 @@ def test_packer_folds_match_float64(k, ms, out):
     b2_off = 131072 + 512 * out
     assert np.array_equal(pol.packed_host[b2_off:b2_off + 1024].view(np.float32), layers[1][1])
     assert np.array_equal(pol.packed_host[b2_off + 1024:b2_off + 1024 + 4 * out].view(np.float32), layers[2][1])
+
+
+def test_q_scale_touches_the_query_third_only():
+    k, ms, out = ar.SAT_SHAPE
+    p0, l0 = ar.make_attn(k, ms, out, seed_offset=1)
+    p1, l1 = ar.make_saturated()
+    for name in ar.NAMES[4:6]:
+        assert np.array_equal(p1[name][:32], p0[name][:32] * np.float32(ar.SAT_Q_SCALE))
+        assert np.array_equal(p1[name][32:], p0[name][32:])  # Wk, Wv, bk, bv as they were
+    for name in ar.NAMES[:4] + ar.NAMES[6:]:
+        assert np.array_equal(p1[name], p0[name])
+    for (w1, b1), (w0, b0) in zip(l1, l0):
+        assert np.array_equal(w1, w0) and np.array_equal(b1, b0)
+    f0, f1 = ar.folds64(p0, l0), ar.folds64(p1, l1)
+    assert np.array_equal(f1["F"], f0["F"]) and np.array_equal(f1["d"], f0["d"])  # the folded first layer keeps its size
+    # the score matrix grows 144-fold (Wq x 144 is rounded to f32: 2^-24 per product, against the largest entry)
+    assert np.abs(f1["A"] - ar.SAT_Q_SCALE * f0["A"]).max() <= 1e-6 * np.abs(f1["A"]).max()
+
+
+def test_saturated_fixture_premises():
+    """What tests/test_gpu_attn_shapes.py::test_saturated_softmax_in_score_order relies on."""
+    k, ms, out = ar.SAT_SHAPE
+    params, layers = ar.make_saturated()
+    x, score = ar.saturated_rows(params, layers)
+    assert len(x) >= ar.SAT_ROWS == 97
+    assert len(ar.saturated_rows(params, layers, pool=4096)[0]) == 71  # 8192 is the smallest power of two that serves
+    srt = np.sort(score, axis=1)
+    assert (srt[:, -1] - srt[:, 0]).min() > 104 and (srt[:, -1] - srt[:, -2]).min() > 30
+    assert np.exp(np.float32(-104.0)) == 0  # f32: the lowest slot's weight underflows
+    var = ar.saturated_variants(params, layers)
+    refs = {}
+    for name, xv in var.items():
+        assert xv.shape == (97, 93) and xv.dtype == np.float32
+        refs[name], sc, a = ar.forward64(params, layers, k, xv, details=True)
+        assert np.array_equal(np.sort(sc, axis=1), srt)  # a slot's score does not depend on its position
+        assert a.max(axis=1).min() > 1 - 1e-12
+        if name == "ascending":
+            assert np.all(np.diff(sc, axis=1) > 0)
+        if name == "descending":
+            assert np.all(np.diff(sc, axis=1) < 0)
+        assert np.array_equal(xv[:, :9], x[:, :9]) and np.array_equal(xv[:, 9 + 4 * k:], x[:, 9 + 4 * k:])
+    assert np.array_equal(var["drawn"], x)
+    assert not np.array_equal(var["ascending"], x) and not np.array_equal(var["descending"], x)
+    assert np.array_equal(var["ascending"][:, 9:9 + 4 * k].reshape(97, k, 4)[:, ::-1],
+                          var["descending"][:, 9:9 + 4 * k].reshape(97, k, 4))
+    spread = max(np.abs(refs[n] - refs["drawn"]).max() for n in ("ascending", "descending"))
+    print(f"saturated: scores up to {score.max():.1f}, span up to {(srt[:, -1] - srt[:, 0]).max():.1f}, "
+          f"variants' ref64 within {spread:.1e} (bound 1e-12)")
+    assert spread <= 1e-12
+
+
+@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12)] + list(ar.MORE_SHAPES))
+def test_sampling_fixtures_keep_log_std_in_range(k, ms, out):
+    """The premise of test_sampling_with_real_weights (-2 <= log_std <= 0.5), on both references."""
+    params, layers = ar.make_attn(k, ms, out, log_std_scale=0.25)
+    x = ar.obs_set(k, ms)
+    for lg in (ar.forward64(params, layers, k, x), ar.forward_bf16_emu(params, layers, k, ms, x)):
+        ls = lg[:, out // 2:]
+        assert -2.0 + 0.1 <= ls.min() and ls.max() <= 0.5 - 0.1, (ls.min(), ls.max())
 
 
 def test_state_dict_names_and_round_trip():

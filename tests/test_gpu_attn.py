@@ -1,7 +1,8 @@
 """GPU: the attention actor's kernels (csrc/swarm_attn.hip) against tests/attn_ref.py, through
 `AttentionPolicy`, `RolloutCollector` and `PPOLearner`.
 
-Shapes (K, Ms, out) = attn_ref.SHAPES and row counts 1, 33, 257 (a lone row, one past a 32-row tile,
+Shapes (K, Ms, out) = attn_ref.SHAPES + attn_ref.MORE_SHAPES (the latter: the logits widths 4, 8, 10
+and sensed_obstacles 2, 3) and row counts 1, 33, 257 (a lone row, one past a 32-row tile,
 one past a 256-row workgroup; 33 and 257 also leave the second 32-row tile of a wave's 64 rows with
 a single row, 1 leaves it empty).  One 257-row reference per shape; the smaller counts are prefixes.
 
@@ -11,9 +12,13 @@ Bounds:
   bf16  max |got - emu| <= 1e-3 (emu: attn_ref.forward_bf16_emu, the rounding points of DESIGN.md
         §3.3), and max |got - ref64| <= max |emu - ref64| + 1e-3.
 Measured on an MI355X (DESIGN.md §5.4): f32 at most 9.4e-7 (0.0085 of the bound, the collector's rows);
-bf16 against the emulation at most 1.5e-5 on the plain fixtures, 1.15e-4 after load_params, 7.7e-4 on
-the peaked fixture (whose 12 x larger folded weights amplify every flipped bf16 rounding of s);
-recovered normals within 6.3e-7 of sample_noise64.
+bf16 against the emulation at most 1.5e-5 on the SHAPES fixtures, 4.1e-4 on MORE_SHAPES ((11,5,10):
+three rows with one hidden activation each on a bf16 rounding tie, every other row within 1.1e-7),
+1.15e-4 after load_params, 7.7e-4 on the peaked fixture (whose 12 x larger folded weights amplify
+every flipped bf16 rounding of s); recovered normals within 7.0e-7 of sample_noise64.
+
+More than one workgroup and grid pass, slot order on a saturated softmax, row independence, unaligned
+views, streams and the bf16 collector: tests/test_gpu_attn_shapes.py.
 """
 from __future__ import annotations
 
@@ -38,10 +43,10 @@ def dev():
 
 
 @functools.lru_cache(maxsize=None)
-def _case(k, ms, out, in_proj_scale=1.0, seed_offset=0, log_std_scale=None):
+def _case(k, ms, out, in_proj_scale=1.0, seed_offset=0, log_std_scale=None, q_scale=1.0):
     """(params, layers, obs, ref64, emu): computed once per fixture, never modified."""
     params, layers = ar.make_attn(k, ms, out, in_proj_scale=in_proj_scale, seed_offset=seed_offset,
-                                  log_std_scale=log_std_scale)
+                                  log_std_scale=log_std_scale, q_scale=q_scale)
     x = ar.obs_set(k, ms)
     ref = ar.forward64(params, layers, k, x)
     emu = ar.forward_bf16_emu(params, layers, k, ms, x)
@@ -73,7 +78,7 @@ def check_bf16(got, emu, ref, tag):
     assert e_ref <= floor + 1e-3, (tag, e_ref, floor)
 
 
-@pytest.mark.parametrize("k,ms,out", ar.SHAPES)
+@pytest.mark.parametrize("k,ms,out", ar.SHAPES + ar.MORE_SHAPES)
 def test_f32_logits(dev, k, ms, out):
     params, layers, x, ref, _ = _case(k, ms, out)
     pol = _policy(dev, params, layers, k, ms, "f32")
@@ -84,7 +89,7 @@ def test_f32_logits(dev, k, ms, out):
         check_f32(got, ref[:rows], f"K={k} Ms={ms} out={out} rows={rows}")
 
 
-@pytest.mark.parametrize("k,ms,out", ar.SHAPES)
+@pytest.mark.parametrize("k,ms,out", ar.SHAPES + ar.MORE_SHAPES)
 def test_bf16_logits(dev, k, ms, out):
     params, layers, x, ref, emu = _case(k, ms, out)
     pol = _policy(dev, params, layers, k, ms, "bf16")
@@ -133,7 +138,7 @@ def _guarded(dev, rows, width):
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f32"])
-@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12), (6, 0, 2)])
+@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12), (6, 0, 2)] + list(ar.MORE_SHAPES))
 def test_deterministic_actions_and_canaries(dev, precision, k, ms, out):
     params, layers, x, _, _ = _case(k, ms, out)
     pol = _policy(dev, params, layers, k, ms, precision)
@@ -160,7 +165,7 @@ def test_deterministic_actions_and_canaries(dev, precision, k, ms, out):
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f32"])
-@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12), (6, 0, 2)])
+@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12), (6, 0, 2)] + list(ar.MORE_SHAPES))
 def test_sampling_draws_the_policy_normals(dev, precision, k, ms, out):
     """W3 = 0, b3 = 0: mean 0 and std 1, so the actions are the normals themselves — bit for bit those
     of a zero-weight PolicyMLP at the same (seed, counter, rows)."""
@@ -184,7 +189,7 @@ def test_sampling_draws_the_policy_normals(dev, precision, k, ms, out):
 
 
 @pytest.mark.parametrize("precision", ["bf16", "f32"])
-@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12)])
+@pytest.mark.parametrize("k,ms,out", [(3, 4, 6), (16, 5, 12)] + list(ar.MORE_SHAPES))
 def test_sampling_with_real_weights(dev, precision, k, ms, out):
     params, layers, x, _, _ = _case(k, ms, out, log_std_scale=0.25)
     pol = _policy(dev, params, layers, k, ms, precision)
@@ -238,12 +243,12 @@ CFG = dict(max_steps=5, goal_radius=6.0)
 E, N = 8, 4
 
 
-def _rollout(dev, horizon):
+def _rollout(dev, horizon, precision="f32"):
     from swarm_marl_amd import CriticMLP, RolloutCollector, VecSwarm
     vec = VecSwarm(E, dict(CFG, num_drones=N), device=dev, auto_reset=True, seed=11, with_global_state=True)
     vec.reset()
     params, layers, _, _, _ = _case(3, 4, 6, log_std_scale=0.25)
-    policy = _policy(dev, params, layers, 3, 4, "f32")
+    policy = _policy(dev, params, layers, 3, 4, precision)
     critic = CriticMLP(cr.make_critic(6 * N + 3, seed=2), device=dev, precision="f32")
     return RolloutCollector(vec, policy, critic, horizon=horizon, seed=3), policy, critic, params, layers
 
