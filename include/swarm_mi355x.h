@@ -454,6 +454,66 @@ int swarm_gae(const float* reward, const float* value, const uint8_t* terminated
               float* advantage, float* value_target, void* hip_stream);
 
 /*
+ * On-device per-agent critic (csrc/swarm_value.hip): the value tower of RLlib's default TorchFC with
+ * vf_share_layers=False (the reference's build_multi_agent_ppo_config / build_single_agent_ppo_config,
+ * src/swarm_marl/training/config_builders.py: fcnet_hiddens [256, 256], relu), evaluated on each
+ * agent's own observation row:
+ *     value[r] = W3 relu(W2 relu(W1 obs[r] + b1) + b2) + b3          (obs -> 256 -> 256 -> 1)
+ * in_dim is 1 .. SWARM_POLICY_MAX_IN (anything else: SWARM_ELIMIT).  precision:
+ *   SWARM_POLICY_BF16  the actor kernel's design with a one-output last layer: the whole blob
+ *       (W1 and W2 in MFMA-fragment order, b2, w3, b3: 157,712 B) is staged in LDS once per
+ *       workgroup; one wave per 32-row tile computes layers 1 and 2 transposed on
+ *       v_mfma_f32_32x32x16_bf16 (bf16 operands, f32 accumulation; the layer-1 bias rides in the pad
+ *       column k = in_dim, x = 1; relu'd accumulators re-rounded to bf16 are layer 2's B operand);
+ *       layer 3 is relu(h2) rounded to bf16 times the bf16-rounded w3 in f32 on the VALU (no fused
+ *       multiply-add), summed per lane over out blocks 0 .. 7 and registers 0 .. 15 in that order,
+ *       the two lane halves joined by one cross-half add, plus b3.  A value depends on its own row
+ *       only: the same row gives the same bits wherever it sits in a tile or in the grid.
+ *   SWARM_POLICY_F32   parity with an f32 learner, no speed claim: swarm_critic_pack's f32 blob and
+ *       swarm_critic_forward's f32 kernel at this in_dim.
+ *   SWARM_POLICY_F32X3 is rejected with SWARM_ELIMIT.
+ * Rows past `rows` are read from clamped addresses and never written.
+ */
+typedef struct swarm_value {
+  int32_t in_dim;        /* observation width D */
+  int32_t precision;     /* SWARM_POLICY_BF16 / SWARM_POLICY_F32 */
+  const void* weights;   /* device copy of the swarm_value_pack blob (16-B aligned) */
+} swarm_value_t;
+
+/* Bytes of the packed weight blob (negative SWARM_E* code if unsupported). */
+long long swarm_value_packed_bytes(int in_dim, int precision);
+
+/* Pack row-major f32 weights (PyTorch layout: w1 [256,in], w2 [256,256], w3 [1,256]) into the
+ * kernel's blob at host_out (host memory). */
+int swarm_value_pack(int in_dim, int precision, const float* w1, const float* b1, const float* w2,
+                     const float* b2, const float* w3, const float* b3, void* host_out);
+
+/* value [rows] for obs [rows,in_dim]; async on hip_stream, no allocation, no sync.  rows == 0 is a
+ * no-op. */
+int swarm_value_forward(const swarm_value_t* v, const float* obs, long long rows, float* value, void* hip_stream);
+
+/*
+ * swarm_gae with a per-agent value [T+1,E,N] (row t: V(obs[t,e,n]) before step t; row T bootstraps
+ * the fragment end).  One thread per (e, n) walks t = T-1 .. 0 in f32, in exactly this order (no
+ * fused multiply-add):
+ *     gl = gamma * lam;  carry = 0
+ *     if !valid[t,e,n]: advantage = value_target = 0; carry = 0; continue
+ *     done  = terminated[t,e,n] | truncated[t,e,n] | (env_done[t,e] & (TERMINATED | TRUNCATED)) != 0
+ *     nv    = done ? 0 : value[t+1,e,n];   prev = done ? 0 : carry
+ *     delta = (reward[t,e,n] + gamma * nv) - value[t,e,n]
+ *     carry = delta + gl * prev
+ *     advantage[t,e,n] = carry;  value_target[t,e,n] = carry + value[t,e,n]
+ * value[t,e,n] is not read when valid[t,e,n] == 0, value[t+1,e,n] is not read when the step is
+ * invalid or done (either may be NaN).  Any episode end stops the bootstrap, a truncation included.
+ * Async; errors via swarm_value_last_error.
+ */
+int swarm_gae_agent(const float* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated,
+                    const uint8_t* env_done, const uint8_t* valid, int T, int E, int N, float gamma, float lam,
+                    float* advantage, float* value_target, void* hip_stream);
+
+const char* swarm_value_last_error(void);
+
+/*
  * PPO loss head (csrc/swarm_ppo.hip): RLlib's PPOTorchPolicy.loss over a collected fragment, value
  * and gradient in one pass.  Rows are grouped by env-row: an env-row is one (t, e) with its N
  * consecutive agent rows (the collector's [T,E,N,...] flatten); values are per env-row.

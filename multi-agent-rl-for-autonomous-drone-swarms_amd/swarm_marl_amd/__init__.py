@@ -4,15 +4,17 @@ Host side of the C-ABI in include/swarm_mi355x.h.  `VecSwarm` is the batched ten
 `envs` holds the reference-compatible RLlib / Gymnasium classes; `CriticMLP` and `RolloutCollector`
 (with `gaussian_logp` and `gae`) turn a device rollout into a PPO-ready batch; `PPOLearner` (with
 `ppo_loss` and `masked_moments`) trains on it.  `AttentionPolicy` is the reference's attention actor
-on the device, `AttentionActor` its trainable torch module.
+on the device, `AttentionActor` its trainable torch module.  `AgentValueMLP` (with `gae_agent`) is the
+per-agent critic of the reference's multi-agent and single-agent PPO set-ups.
 """
 from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .envs.common import DroneEnvConfig
 from .ppo import PPOLearner, masked_moments, ppo_loss
-from .rollout import RolloutCollector, gae, gaussian_logp
+from .rollout import RolloutCollector, gae, gae_agent, gaussian_logp
+from .value import AgentValueMLP
 from .vec_env import VecSwarm
 
-__all__ = ["AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner", "RolloutCollector",
-           "VecSwarm", "gae", "gaussian_logp", "masked_moments", "ppo_loss"]
+__all__ = ["AgentValueMLP", "AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner",
+           "RolloutCollector", "VecSwarm", "gae", "gae_agent", "gaussian_logp", "masked_moments", "ppo_loss"]
 __version__ = "0.1.0"

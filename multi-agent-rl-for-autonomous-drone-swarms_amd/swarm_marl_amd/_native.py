@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "swarm_attn_policy_last_error",
     "swarm_eval_begin", "swarm_eval_update", "swarm_eval_single_update", "swarm_eval_last_error",
     "swarm_env_cfg_set",
+    "swarm_value_packed_bytes", "swarm_value_pack", "swarm_value_forward", "swarm_gae_agent", "swarm_value_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
     "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
@@ -86,6 +87,7 @@ EXPORTED_SYMBOLS = (
 ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-9:-3]
 PPO_SYMBOLS = EXPORTED_SYMBOLS[-3:]
 ATTN_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_attn_"))  # csrc/swarm_attn.hip
+VALUE_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_value_")) + ("swarm_gae_agent",)  # csrc/swarm_value.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -181,6 +183,11 @@ class SwarmAttnWeights(ctypes.Structure):
 
 
 class SwarmCritic(ctypes.Structure):
+    _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
+class SwarmValue(ctypes.Structure):
+    """swarm_value_t."""
     _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
 
 
@@ -291,6 +298,18 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.swarm_gae.restype = ctypes.c_int
         lib.swarm_gae.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_float, ctypes.c_float, vp, vp, vp]
+    if path is None or all(hasattr(lib, name) for name in VALUE_SYMBOLS):
+        lib.swarm_value_packed_bytes.restype = ctypes.c_longlong
+        lib.swarm_value_packed_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        lib.swarm_value_pack.restype = ctypes.c_int
+        lib.swarm_value_pack.argtypes = [ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, vp]
+        lib.swarm_value_forward.restype = ctypes.c_int
+        lib.swarm_value_forward.argtypes = [ctypes.POINTER(SwarmValue), vp, ctypes.c_longlong, vp, vp]
+        lib.swarm_gae_agent.restype = ctypes.c_int
+        lib.swarm_gae_agent.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_float, ctypes.c_float, vp, vp, vp]
+        lib.swarm_value_last_error.restype = ctypes.c_char_p
+        lib.swarm_value_last_error.argtypes = []
     if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
         lib.swarm_masked_moments.restype = ctypes.c_int
         lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -309,13 +328,13 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 def check(rc: int, lib: ctypes.CDLL | None = None, policy: bool = False, which: str | None = None) -> None:
     """Raise on a negative return code (bad arguments -> ValueError, HIP errors -> RuntimeError).
     `which` names the component whose last-error string explains it ("policy", "attn", "eval", "critic",
-    "ppo")."""
+    "ppo", "value")."""
     if rc == SWARM_OK:
         return
     lib = lib or load_library()
     which = "policy" if policy else which
     err = (lib.swarm_critic_last_error if which == "critic" else lib.swarm_ppo_last_error if which == "ppo" else
-           lib.swarm_attn_policy_last_error if which == "attn" else
+           lib.swarm_attn_policy_last_error if which == "attn" else lib.swarm_value_last_error if which == "value" else
            {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error))
     msg = (err() or b"").decode(errors="replace")
     if rc in (SWARM_EINVAL, SWARM_ENULL, SWARM_ELIMIT):

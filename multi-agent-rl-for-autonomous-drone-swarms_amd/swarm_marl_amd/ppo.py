@@ -13,7 +13,8 @@ statistics (swarm_masked_moments).  `PPOLearner` runs the update of a RolloutCol
     info = learner.update(col.collect())       # policy / critic now hold the new weights
 
 Rows are grouped by env-row — one (t, e) with its N agents, the collector's [T, E, N, ...] flatten —
-and values are per env-row.
+and values are per env-row.  With an `AgentValueMLP` as the critic the value net runs
+on the minibatch's obs rows and the head is called with one value per agent row (num_agents = 1).
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
 from .rollout import _F32, _U8, _check, _stream
+from .value import AgentValueMLP
 
 STATS = ("count", "total_loss", "policy_loss", "vf_loss", "entropy", "kl", "clip_frac")
 _F64 = (torch.float64,)
@@ -168,12 +170,20 @@ class PPOLearner:
     (x 1.5 above 2 x kl_target, x 0.5 below 0.5 x kl_target; the update's one read of a device
     result) and the new weights pushed into `policy` / `critic` in place (`load_layers`: the packers
     are host code, so the weights pass through host memory once per update).
+
+    With an `AgentValueMLP` as `critic` (the per-agent value tower of the reference's multi-agent and
+    single-agent PPO set-ups) `value_net` is D -> 256 -> 256 -> 1 on the minibatch's obs rows, `ppo_loss`
+    gets one value per agent row, and a fragment without `global_state` is accepted.
     """
 
-    def __init__(self, policy: PolicyMLP, critic: CriticMLP, *, lr: float = 3e-4, num_epochs: int = 10,
+    def __init__(self, policy: PolicyMLP, critic: CriticMLP | AgentValueMLP, *, lr: float = 3e-4, num_epochs: int = 10,
                  minibatch_env_rows: int, kl_target: float = 0.01, seed: int = 0, **loss_kw):
-        if not isinstance(policy, (PolicyMLP, AttentionPolicy)) or not isinstance(critic, CriticMLP):
+        if not isinstance(policy, (PolicyMLP, AttentionPolicy)) or not isinstance(critic, (CriticMLP, AgentValueMLP)):
             raise ValueError("PPOLearner needs a PolicyMLP and a CriticMLP")
+        self.per_agent = isinstance(critic, AgentValueMLP)
+        if self.per_agent and critic.in_dim != policy.in_dim:
+            raise ValueError(f"the per-agent critic takes {critic.in_dim} inputs, the policy's observations are "
+                             f"{policy.in_dim} wide")
         if policy.device != critic.device:
             raise ValueError(f"policy is on {policy.device}, critic on {critic.device}")
         if policy.out_dim % 2 or not 1 <= policy.out_dim // 2 <= nat.PPO_MAX_ACT:
@@ -213,20 +223,31 @@ class PPOLearner:
     def update(self, batch: dict) -> dict:
         """One PPO update from a `RolloutCollector.collect()` dict.  Returns the last epoch's mean
         stats (`STATS` keys, floats), `epoch_total_loss` (the mean total loss of every epoch) and
-        the new `kl_coeff`."""
+        the new `kl_coeff`.  Minibatches stay grouped by env-row in either critic mode: a minibatch is
+        `minibatch_env_rows` whole (t, e) rows with all their N agents, also when the value is per agent."""
         valid = batch["valid"]
+        if self.per_agent:
+            return self._update(batch, 0)
         if batch.get("global_state") is None:
             raise ValueError("the fragment has no global_state: collect with VecSwarm(..., with_global_state=True)")
+        return self._update(batch, int(batch["global_state"].shape[-1]))
+
+    def _update(self, batch: dict, g: int) -> dict:
+        """`update` for a fragment whose global_state is g wide; g = 0: the per-agent critic, which
+        reads no global_state."""
+        valid = batch["valid"]
         t, e, n = (int(s) for s in valid.shape)
-        d, a, g = int(batch["obs"].shape[-1]), int(batch["actions"].shape[-1]), int(batch["global_state"].shape[-1])
-        if d != self.policy.in_dim or 2 * a != self.policy.out_dim or g != self.critic.in_dim:
+        d, a = int(batch["obs"].shape[-1]), int(batch["actions"].shape[-1])
+        if d != self.policy.in_dim or 2 * a != self.policy.out_dim or (g if g else d) != self.critic.in_dim:
             raise ValueError(f"fragment is obs {d} / actions {a} / global_state {g} wide, the learner's networks take "
                              f"{self.policy.in_dim} / {self.policy.out_dim // 2} / {self.critic.in_dim}")
         te = t * e
         src = dict(obs=batch["obs"].reshape(te, n, d), behaviour_logits=batch["logits"].reshape(te, n, 2 * a),
                    actions=batch["actions"].reshape(te, n, a), logp=batch["logp"].reshape(te, n),
                    advantage=batch["advantage"].reshape(te, n), value_target=batch["value_target"].reshape(te, n),
-                   valid=valid.reshape(te, n), global_state=batch["global_state"][:t].reshape(te, g))
+                   valid=valid.reshape(te, n))
+        if g:
+            src["global_state"] = batch["global_state"][:t].reshape(te, g)
         buf = self._buffers(n, d, a, g)
         masked_moments(batch["advantage"], valid, out=self._adv_moments)
         mb = self.minibatch_env_rows
@@ -237,12 +258,13 @@ class PPOLearner:
             for i in range(nmb):
                 idx = perm[i * mb:(i + 1) * mb]
                 m = int(idx.numel())
-                cur = {k: buf[k][:m] for k in buf}
+                cur = {k: buf[k][:m] for k in src}
                 for k in cur:
                     torch.index_select(src[k], 0, idx, out=cur[k])
                 masked_moments(cur["advantage"], cur["valid"], out=self._valid_moments)
                 logits = self.actor(cur["obs"].view(m * n, d))
-                value = self.value_net(cur["global_state"]).view(m)
+                value = (self.value_net(cur["global_state"]).view(m) if g else
+                         self.value_net(cur["obs"].view(m * n, d)).view(m * n))
                 loss, stats = ppo_loss(logits, value, behaviour_logits=cur["behaviour_logits"], actions=cur["actions"],
                                        logp=cur["logp"], advantage=cur["advantage"], value_target=cur["value_target"],
                                        valid=cur["valid"], adv_moments=self._adv_moments,

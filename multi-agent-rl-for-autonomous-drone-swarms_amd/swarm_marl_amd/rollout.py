@@ -17,6 +17,12 @@ auto-reset has already replaced the state); only the fragment end (row T) bootst
 is the env's active mask before step t: an agent that ended earlier in a still-running episode
 takes no step and gets zero advantage and target.  Without a critic the values are zero, so the
 advantages (and targets) are the rewards-to-go discounted by gamma * lam, cut at episode ends.
+
+With an `AgentValueMLP` as `critic` (the per-agent value tower of the reference's
+multi-agent and single-agent PPO set-ups) the value is per agent, V(obs[t, e, n]): the observations
+go into one [T+1, E, N, D] block (row T: the env's obs after the last step), one value launch runs
+over the whole block and `gae_agent` reads value[t, e, n].  The bootstrap rules are the same; no
+global_state is needed.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ from . import _native as nat
 from .attention import AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
+from .value import AgentValueMLP
 from .vec_env import VecSwarm
 
 
@@ -94,6 +101,34 @@ def gae(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, tru
     return advantage, value_target
 
 
+def gae_agent(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor,
+              env_done: torch.Tensor, valid: torch.Tensor, *, gamma: float = 0.99, lam: float = 0.95,
+              advantage: torch.Tensor | None = None, value_target: torch.Tensor | None = None):
+    """`gae` with a per-agent value [T+1, E, N] (swarm_gae_agent; the loop in include/swarm_mi355x.h,
+    bit for bit an f32 NumPy loop).  value[t, e, n] of an invalid step and value[t+1, e, n] behind an
+    invalid or done step are never read."""
+    if not isinstance(reward, torch.Tensor) or reward.dim() != 3:
+        raise ValueError("reward must be a tensor [T, E, N]")
+    t, e, n = (int(s) for s in reward.shape)
+    dev = reward.device
+    _check("reward", reward, (t, e, n), _F32)
+    _check("value", value, (t + 1, e, n), _F32, dev)
+    for name, x in (("terminated", terminated), ("truncated", truncated), ("valid", valid)):
+        _check(name, x, (t, e, n), _U8, dev)
+    _check("env_done", env_done, (t, e), _U8, dev)
+    if advantage is None:
+        advantage = torch.empty((t, e, n), dtype=torch.float32, device=dev)
+    if value_target is None:
+        value_target = torch.empty((t, e, n), dtype=torch.float32, device=dev)
+    _check("advantage", advantage, (t, e, n), _F32, dev)
+    _check("value_target", value_target, (t, e, n), _F32, dev)
+    lib = nat.load_library()
+    nat.check(lib.swarm_gae_agent(reward.data_ptr(), value.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                  env_done.data_ptr(), valid.data_ptr(), t, e, n, float(gamma), float(lam),
+                                  advantage.data_ptr(), value_target.data_ptr(), _stream(dev)), lib, which="value")
+    return advantage, value_target
+
+
 class RolloutCollector:
     """Collects fragments of `horizon` steps from `vec` under `policy` (a `PolicyMLP` or an
     `AttentionPolicy`: anything with their in_dim / out_dim / device and forward); see the module
@@ -103,9 +138,12 @@ class RolloutCollector:
       obs [T,E,N,D], logits [T,E,N,out], actions [T,E,N,out/2], logp / reward / advantage /
       value_target [T,E,N] f32, terminated / truncated / valid [T,E,N] bool, env_done [T,E] u8,
       global_state [T+1,E,G] and value [T+1,E] (row t: before step t; row T: after the last step).
+    With an `AgentValueMLP` as `critic`: value [T+1,E,N], and obs is the first-T view of `obs_block`
+    [T+1,E,N,D] (row T: the obs after the last step); global_state only if the env has one.
     """
 
-    def __init__(self, vec: VecSwarm, policy: PolicyMLP | AttentionPolicy, critic: CriticMLP | None = None, *, horizon: int,
+    def __init__(self, vec: VecSwarm, policy: PolicyMLP | AttentionPolicy, critic: CriticMLP | AgentValueMLP | None = None, *,
+                 horizon: int,
                  gamma: float = 0.99, lam: float = 0.95, seed: int = 0):
         t = int(horizon)
         if t < 1:
@@ -117,7 +155,12 @@ class RolloutCollector:
         if policy.device != vec.device:
             raise ValueError(f"policy is on {policy.device}, the env on {vec.device}")
         g = 6 * n + 3
-        if critic is not None:
+        self.per_agent = isinstance(critic, AgentValueMLP)
+        if self.per_agent:
+            if critic.in_dim != d or critic.device != vec.device:
+                raise ValueError(f"the per-agent critic takes {critic.in_dim} inputs on {critic.device}, the env's obs "
+                                 f"is {d} wide on {vec.device}")
+        elif critic is not None:
             if vec.global_state is None:
                 raise ValueError("a critic needs the env's global_state: VecSwarm(..., with_global_state=True)")
             if critic.in_dim != g or critic.device != vec.device:
@@ -129,7 +172,8 @@ class RolloutCollector:
         kw = dict(device=vec.device)
         f32 = torch.float32
         out = policy.out_dim
-        self.obs = torch.zeros((t, e, n, d), dtype=f32, **kw)
+        self.obs_block = torch.zeros((t + 1, e, n, d), dtype=f32, **kw) if self.per_agent else None
+        self.obs = self.obs_block[:t] if self.per_agent else torch.zeros((t, e, n, d), dtype=f32, **kw)
         self.logits = torch.zeros((t, e, n, out), dtype=f32, **kw)
         self.actions = torch.zeros((t, e, n, out // 2), dtype=f32, **kw)
         self.logp = torch.zeros((t, e, n), dtype=f32, **kw)
@@ -141,7 +185,7 @@ class RolloutCollector:
         self.value_target = torch.zeros((t, e, n), dtype=f32, **kw)
         self.env_done = torch.zeros((t, e), dtype=torch.uint8, **kw)
         self.global_state = torch.zeros((t + 1, e, g), dtype=f32, **kw) if vec.global_state is not None else None
-        self.value = torch.zeros((t + 1, e), dtype=f32, **kw)
+        self.value = torch.zeros((t + 1, e, n) if self.per_agent else (t + 1, e), dtype=f32, **kw)
         self._batch = {k: getattr(self, k) for k in
                        ("obs", "logits", "actions", "logp", "reward", "terminated", "truncated", "valid",
                         "advantage", "value_target", "env_done", "global_state", "value")}
@@ -166,9 +210,16 @@ class RolloutCollector:
             self.env_done[t].copy_(env_done)
         if self.global_state is not None:
             self.global_state[self.horizon].copy_(vec.global_state)
-        if self.critic is not None:
+        if self.per_agent:
+            self.obs_block[self.horizon].copy_(vec.obs)
+            self.critic.value(self.obs_block, out=self.value)
+        elif self.critic is not None:
             self.critic.value(self.global_state, out=self.value)
         gaussian_logp(self.logits, self.actions, out=self.logp)
+        if self.per_agent:
+            gae_agent(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid,
+                      gamma=self.gamma, lam=self.lam, advantage=self.advantage, value_target=self.value_target)
+            return self._batch
         gae(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid,
             gamma=self.gamma, lam=self.lam, advantage=self.advantage, value_target=self.value_target)
         return self._batch
