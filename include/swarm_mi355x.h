@@ -147,8 +147,9 @@ typedef struct swarm_state {
  * domain randomisation configs/domain_randomization_v1.yaml:9-57 as per-env tensors).  One 64-B
  * record per env, derived on the device by swarm_env_cfg_set from per-env values exactly as the
  * library derives the uniform constants from swarm_params_t, so that an env with record r behaves
- * bit-for-bit like a launch whose swarm_params_t carries r's values.  N, K, Ms, rewards and radii
- * other than the obstacle radius stay uniform (they fix the tensor shapes or are not randomised).
+ * bit-for-bit like a launch whose swarm_params_t carries r's values.  K, Ms, rewards and radii
+ * other than the obstacle radius stay uniform (they fix the tensor shapes or are not randomised);
+ * N fixes the slots per env, of which an env may use fewer (num_drones).
  * With env_cfg set, swarm_step launches the generic kernel (the step64 specialisation assumes
  * uniform parameters).
  */
@@ -165,7 +166,9 @@ typedef struct swarm_env_cfg {
   int32_t max_steps;
   int32_t num_obstacles; /* active obstacles, 0..swarm_params_t.num_obstacles (the state keeps M
                             slots; slots >= num_obstacles are zero and ignored) */
-  int32_t reserved;
+  int32_t num_drones;    /* drones of this env, 1..swarm_params_t.num_drones; 0 (what swarm_env_cfg_set
+                            writes) = all of them.  Slots >= num_drones do not exist: see
+                            swarm_env_cfg_set_drones */
   double max_speed_d;    /* max_speed as given (physics observation clamp) */
   double world_size;     /* as given (for readers) */
 } swarm_env_cfg_t;
@@ -610,6 +613,11 @@ const char* swarm_ppo_last_error(void);
 #define SWARM_EVAL_LIVE 1u       /* status: an episode is being accumulated */
 #define SWARM_EVAL_COLLIDED 2u   /* status: an observed agent reported a collision */
 #define SWARM_EVAL_STEP_FUSED 1  /* swarm_eval_t.flags: per-step accumulation done by the step (out.eval) */
+#define SWARM_EVAL_SLOT_COUNTS 2 /* swarm_eval_t.flags: the batch has per-env drone counts (swarm_env_cfg_set_drones):
+                                    a slot not stepped on an episode's first step is no drone of that
+                                    episode (every drone of a fresh episode is stepped) and is left out of
+                                    its path-efficiency mean (traveled[e][slot] = -1 marks it); begin the
+                                    tracker at episode starts.  Unfused updates only */
 #define SWARM_EVAL_RECORD 9      /* doubles per record: global env index, success, collision_free, time_to_goal
                                     (NaN if never all-reached), formation_error, path_efficiency,
                                     episode_reward, steps, update_index of the closing update */
@@ -634,7 +642,8 @@ typedef struct swarm_eval {
                              rest are dropped) */
   int32_t capacity;       /* a multiple of `segments` */
   int32_t update_index;   /* stamped into the records this update closes (the caller counts updates) */
-  int32_t flags;          /* SWARM_EVAL_STEP_FUSED: the step launches carry this state in out.eval */
+  int32_t flags;          /* SWARM_EVAL_STEP_FUSED: the step launches carry this state in out.eval;
+                             SWARM_EVAL_SLOT_COUNTS: per-env drone counts */
   int32_t seg_base;       /* segment of the tracker's first global env (its env_offset mod 64) */
   int32_t segments;       /* record segments that receive episodes: min(envs, 64) (0 = 64): a
                              batch of E < 64 envs holds only E row blocks */
@@ -672,6 +681,31 @@ const char* swarm_eval_last_error(void);
  */
 int swarm_env_cfg_set(const swarm_params_t* p, const swarm_env_overrides_t* ov, const uint8_t* env_mask,
                       swarm_env_cfg_t* cfg, void* hip_stream);
+
+/*
+ * Per-env drone counts: write cfg[e].num_drones of the masked envs (env_mask NULL = all) from
+ * drones[e] (device int32 [E], clamped to [1, swarm_params_t.num_drones]; drones NULL = every
+ * slot).  Only that field is written, async on hip_stream; swarm_env_cfg_set writes it as 0
+ * (= every slot), so call this after it.
+ *
+ * Env e with count n then behaves exactly like env env_offset + e of a batch built with
+ * num_drones = n: slots 0..n-1 are its drones; slots >= n do not exist — never a neighbour,
+ * never in a collision or formation pair, no vote in any env-level reduction, their actions
+ * ignored (a drone that ended earlier, by contrast, stays a frozen neighbour).  Buffers keep
+ * their N-slot strides.  Every step and reset writes zeros for a slot that does not exist: obs
+ * row, reward, terminated, truncated, active, dist_goal, info_flags, state pos / vel and its
+ * global_state entries (global_state [6N+3] is the zero-padded embedding of the 6n+3 vector);
+ * swarm_observe writes the output zeros and leaves the state alone.  A device reset draws drone t
+ * from Philox block t, obstacle m from block n + m, the goal from block n + num_obstacles[e]: the
+ * blocks of the n-drone batch.
+ *
+ * In env_cfg_next the count takes effect at the env's next reset (auto or explicit), which draws,
+ * activates and observes with it; it may grow or shrink.  Written to env_cfg (the current
+ * episode) it must be followed by a swarm_reset, or by new state, of those envs before their next
+ * step: the step does not read the state of slots >= n, and slots < n must hold drones.
+ */
+int swarm_env_cfg_set_drones(const swarm_params_t* p, const int32_t* drones, const uint8_t* env_mask,
+                             swarm_env_cfg_t* cfg, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -165,8 +165,13 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
   const bool restarts = ends && (done & SWARM_ENV_RESET) != 0;
   // ---- per-agent votes, path length, observed positions; path efficiency and the next
   // episode's start rows when the episode ends here
+  // SWARM_EVAL_SLOT_COUNTS (per-env drone counts): every drone of a fresh episode is stepped on
+  // its first step, so a slot that is not does not exist in this episode; its path length is
+  // marked -1 and the episode's path efficiency is the mean over the slots that exist
+  const bool counts = (v.flags & SWARM_EVAL_SLOT_COUNTS) != 0;
+  const bool first = counts && steps0 == 0;
   double rsum = 0.0, pe = 0.0;
-  int n_st = 0, n_obs = 0, coll = 0, not_reached = 0;
+  int n_st = 0, n_obs = 0, coll = 0, not_reached = 0, n_ex = 0;
   for (int i = t; i < a.N; i += EVAL_THREADS) {
     const size_t r = (size_t)e * a.N + i;
     const uint8_t fl = a.info_flags[r];
@@ -195,9 +200,12 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
       tr += (double)norm1d(lx - ox, ly - oy, lz - oz);
     }
     pos[i] = p;
+    const bool absent = first && !(fl & SWARM_AGENT_STEPPED);
+    if (absent) tr = -1.0;
     if (ends) {
       const float straight = norm1d(sx - gx, sy - gy, sz - gz);
       pe += tr > 1e-8 ? (double)straight / tr : 0.0;
+      n_ex += tr >= 0.0 ? 1 : 0;
     }
     if (restarts) {  // the obs rows are the new episode's first observation (every agent)
       v.start[3 * r] = ox; v.start[3 * r + 1] = oy; v.start[3 * r + 2] = oz;
@@ -207,6 +215,8 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
     } else if (has) {
       v.traveled[r] = tr;
       v.last[3 * r] = ox; v.last[3 * r + 1] = oy; v.last[3 * r + 2] = oz;
+    } else if (absent) {
+      v.traveled[r] = tr;
     }
   }
   // LDS ordering within one wave: a compiler fence around the wave barrier suffices
@@ -286,7 +296,14 @@ __global__ void __launch_bounds__(EVAL_THREADS * EVAL_WG_ENVS) eval_update_kerne
     }
     fe = wave_sum(acc) / (double)n_obs;
   }
-  if (ends) pe = wave_sum(pe) / (double)a.N;
+  if (ends) {  // wave-uniform
+    int den = a.N;
+    if (counts) {
+      den = wave_sum_i(n_ex);
+      if (den == 0) den = a.N;
+    }
+    pe = wave_sum(pe) / (double)den;
+  }
   if (t != 0) return;
   const double ep_reward = ep_reward0 + (n_st > 0 ? rsum / (double)n_st : 0.0);
   const double fe_sum = fe_sum0 + fe;
@@ -396,7 +413,7 @@ int make_args(const swarm_params_t* p, const swarm_eval_t* ev, const swarm_out_t
     return efail(SWARM_ENULL, "an eval state buffer is NULL");
   if ((ev->state_pos == nullptr) != (ev->state_goal == nullptr))
     return efail(SWARM_EINVAL, "state_pos and state_goal go together");
-  if (ev->flags & ~SWARM_EVAL_STEP_FUSED) return efail(SWARM_EINVAL, "unknown eval flags 0x%x", (unsigned)ev->flags);
+  if (ev->flags & ~(SWARM_EVAL_STEP_FUSED | SWARM_EVAL_SLOT_COUNTS)) return efail(SWARM_EINVAL, "unknown eval flags 0x%x", (unsigned)ev->flags);
   if (ev->segments < 0 || ev->segments > SWARM_EVAL_SEGMENTS || ev->seg_base < 0)
     return efail(SWARM_EINVAL, "segments must be in [0, %d] and seg_base >= 0", SWARM_EVAL_SEGMENTS);
   const int nseg = ev->segments > 0 ? ev->segments : SWARM_EVAL_SEGMENTS;

@@ -133,12 +133,15 @@ __device__ __forceinline__ swarm_env_cfg_t uniform_env_cfg(const KParams& P) {
   c.s_phys_obst = P.s_phys_obst;
   c.max_steps = P.max_steps;
   c.num_obstacles = P.M;
-  c.reserved = 0;
+  c.num_drones = 0;
   c.max_speed_d = P.vmax_d;
   c.world_size = 0.0;
   return c;
 }
 __device__ __forceinline__ int clamp_obstacles(int m, int M) { return m < 0 ? 0 : (m > M ? M : m); }
+// drones of an env: its record's count, 0 (a record written without one) or anything outside
+// 1..N meaning the batch's N
+__device__ __forceinline__ int env_drones(int n, int N) { return (n < 1 || n > N) ? N : n; }
 
 // ------------------------------------------------------------------ exact numerics
 // Correctly rounded square roots.  NB: HIP's __fsqrt_rn is v_sqrt_f32 (1 ulp) unless
@@ -775,7 +778,11 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
   if (S.env_cfg != nullptr && env_ok) C = S.env_cfg[env];
   else C = uniform_env_cfg(P);
   int Me = clamp_obstacles(C.num_obstacles, M);  // active obstacles (slots >= Me are ignored)
-  const bool is_agent = env_ok && t < N;
+  // per-env drone count: lanes t < Ne are the env's drones; slots Ne <= t < N do not exist (padding
+  // lanes like t >= N, but with rows in the [E, N, ...] buffers, which get zeros).  N stays the
+  // address stride.  A reset that installs the next episode's record re-derives both (draw_env).
+  int Ne = env_drones(C.num_drones, N);
+  bool is_agent = env_ok && t < Ne;
   float4* ring = reinterpret_cast<float4*>(smem) + team * P.ring;
   float4* obst4 = reinterpret_cast<float4*>(smem + P.off_obst) + team * P.obst_stride;
   float* stage = reinterpret_cast<float*>(smem + P.off_stage);
@@ -907,9 +914,18 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
     if (S.env_cfg_next != nullptr) {  // the next episode's parameters take over
       C = S.env_cfg_next[env];
       Me = clamp_obstacles(C.num_obstacles, M);
+      Ne = env_drones(C.num_drones, N);
+      is_agent = t < Ne;  // draw_env runs for envs of the batch only
     }
     uint32_t w[4];
-    if (t < N) {
+    // not a drone of the new episode (a slot that stops existing included): a padding lane.
+    // (Selects, not a branch of stores through the captures: that form put them in scratch.)
+    const bool gone = t >= Ne;
+    px = gone ? PAD_POS : px; py = gone ? PAD_POS : py; pz = gone ? PAD_POS : pz;
+    vx = gone ? 0.f : vx; vy = gone ? 0.f : vy; vz = gone ? 0.f : vz;
+    act = act && !gone;
+    if constexpr (DYN == DYN_PHYS) damp = gone ? 0.f : damp;
+    if (!gone) {
       draw_block(P, genv, episode_new, (uint32_t)t, w);
       px = uni(w[0], C.neg_half_w, C.width_w);
       py = uni(w[1], C.neg_half_w, C.width_w);
@@ -926,12 +942,12 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
         obst4[m] = make_float4(0.f, 0.f, 0.f, 0.f);
         continue;
       }
-      draw_block(P, genv, episode_new, (uint32_t)(N + m), w);
+      draw_block(P, genv, episode_new, (uint32_t)(Ne + m), w);
       float oz = uni(w[2], C.neg_half_w, C.width_w);
       if constexpr (DYN == DYN_PHYS) oz = fmaxf(oz, 0.5f);
       obst4[m] = make_float4(uni(w[0], C.neg_half_w, C.width_w), uni(w[1], C.neg_half_w, C.width_w), oz, 0.f);
     }
-    draw_block(P, genv, episode_new, (uint32_t)(N + Me), w);
+    draw_block(P, genv, episode_new, (uint32_t)(Ne + Me), w);
     gx = uni(w[0], C.neg_half_w, C.width_w);
     gy = uni(w[1], C.neg_half_w, C.width_w);
     gz = uni(w[2], C.neg_half_w, C.width_w);
@@ -973,8 +989,9 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
   // all-eligible fast path: wave-uniform, needs the nearest neighbour (KS > 0) and no padding
   bool fast = false;
   if constexpr (WAVE) fast = (KS > 0) && (N == L) && __all(elig);
-  // block teams: the rotation pass over the pair-entry ring (N a power of two, kinematic)
-  if constexpr (!WAVE && KS > 0 && DYN == DYN_KIN) fast = P.off_pair > 0 && __syncthreads_and(!is_agent || elig) != 0;
+  // block teams: the rotation pass over the pair-entry ring (N a power of two, kinematic); the ring
+  // has no masks, so every slot of every team must be a drone (Ne == N)
+  if constexpr (!WAVE && KS > 0 && DYN == DYN_KIN) fast = P.off_pair > 0 && __syncthreads_and((!is_agent || elig) && Ne == N) != 0;
   const bool blk_rot = !WAVE && P.off_pair > 0;  // aux / reset passes of block teams rotate too
   if (pass_env) {
     if (mode == MODE_STEP) {
@@ -992,9 +1009,9 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       } else {
         if constexpr (DYN == DYN_KIN) {
           if (fast) pair_pass_block_fast<KS, PASS, false>(pair_ring, N, t, px, py, pz, P.nb_keep, P.ds_f, nk, fsum, smin);
-          else pair_pass_block<KS, PASS>(ring, N, t, px, py, pz, elig, P.nb_keep, P.ds_f, nk, smin, fsum);
+          else pair_pass_block<KS, PASS>(ring, Ne, t, px, py, pz, elig, P.nb_keep, P.ds_f, nk, smin, fsum);
         } else {
-          pair_pass_block<KS, PASS>(ring, N, t, px, py, pz, elig, P.nb_keep, P.ds_f, nk, smin, fsum);
+          pair_pass_block<KS, PASS>(ring, Ne, t, px, py, pz, elig, P.nb_keep, P.ds_f, nk, smin, fsum);
         }
       }
       if constexpr (DYN == DYN_KIN) obstacle_pass<MSL, true>(obst4, Me, px, py, pz, act, C.s_obst, P.ob_keep, ok, ocoll);
@@ -1005,7 +1022,7 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
         else pair_pass_wave<KS, 0, true>(ring, L, t, tid, px, py, pz, true, P.nb_keep, 0.f, nk, smin, fsum);
       } else {
         if (blk_rot) pair_pass_block_fast<KS, 0>(pair_ring, N, t, px, py, pz, P.nb_keep, 0.f, nk, fsum, smin);
-        else pair_pass_block<KS, 0>(ring, N, t, px, py, pz, true, P.nb_keep, 0.f, nk, smin, fsum);
+        else pair_pass_block<KS, 0>(ring, Ne, t, px, py, pz, true, P.nb_keep, 0.f, nk, smin, fsum);
       }
       obstacle_pass<MSL, false>(obst4, Me, px, py, pz, false, 0.f, P.ob_keep, ok, ocoll);
     }
@@ -1027,11 +1044,11 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
     bool slow_nb = false, slow_ob = false;
     if (run) {
       const int imod = rot ? (L - 1) : 0x7fffffff;
-      if constexpr (KS > 0) slow_nb = !finish_keys<KS, false, true>(nk, ring, N, rot ? t : 0, imod, Kq, P.nb_keep, dkey, px, py, pz, wd, wj);
+      if constexpr (KS > 0) slow_nb = !finish_keys<KS, false, true>(nk, ring, Ne, rot ? t : 0, imod, Kq, P.nb_keep, dkey, px, py, pz, wd, wj);
       if constexpr (MSL > 0) slow_ob = !finish_keys<MSL, true, false>(ok, obst4, Me, 0, 0x7fffffff, Mse, P.ob_keep, false, px, py, pz, od, oj);
     }
     if constexpr (KS > 0) {
-      if (slow_nb) exact_select<NW, false>(ring, N, t, Kq, max_first(wd, Kq), px, py, pz, wd, wj);
+      if (slow_nb) exact_select<NW, false>(ring, Ne, t, Kq, max_first(wd, Kq), px, py, pz, wd, wj);
     }
     if constexpr (MSL > 0) {
       if (slow_ob) exact_select<OW, true>(obst4, Me, -1, Mse, max_first(od, Mse), px, py, pz, od, oj);
@@ -1062,13 +1079,13 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
         pcoll = __uint_as_float(nk[0] | ~P.nb_keep) * FAST_HI <= thr;
         if (!pcoll && __uint_as_float(nk[0] & P.nb_keep) * FAST_LO <= thr)
           pcoll = key_zero_hit<DYN == DYN_KIN>(nk[0], P.nb_keep, s_exact_thr) ||
-                  exact_pair_collision(ring, N, t, px, py, pz, s_exact_thr);
+                  exact_pair_collision(ring, Ne, t, px, py, pz, s_exact_thr);
       } else {
         // smin holds d~ (kinematic) or s' (physics): certain below the band, exact inside it
         const float band_thr = (DYN == DYN_KIN) ? d_thr : s_exact_thr;
         pcoll = smin <= band_thr * FAST_LO;
         if (!pcoll && smin <= band_thr * FAST_HI && elig)
-          pcoll = exact_pair_collision(ring, N, t, px, py, pz, s_exact_thr);
+          pcoll = exact_pair_collision(ring, Ne, t, px, py, pz, s_exact_thr);
       }
       if constexpr (DYN == DYN_KIN) {
         const float curr = sqrt_rn(sqsum_1d(gx - px, gy - py, gz - pz));
@@ -1135,8 +1152,8 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       const bool done = any_c || all_goals || tl;
       trunc_all = done && tl && !any_c && !all_goals;
       term_all = done && !trunc_all;
-      term = term_all;
-      trunc = trunc_all;
+      term = term_all && is_agent;  // (padding lanes vote in no packed-byte ballot)
+      trunc = trunc_all && is_agent;
       cont = true;
     }
     do_reset = P.auto_reset && env_ok && (term_all || trunc_all);
@@ -1162,6 +1179,14 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       if (O.info_flags)
         O.info_flags[ag] = (uint8_t)((act ? SWARM_AGENT_STEPPED : 0u) | (act && reached ? SWARM_AGENT_REACHED : 0u) |
                                      (act && collided ? SWARM_AGENT_COLLISION : 0u) | (cont ? SWARM_AGENT_HAS_OBS : 0u));
+    } else if (env_ok && t < N) {  // a slot that was no drone of the episode stepped: zeros
+      O.reward[ag] = 0.f;
+      if (!packed_bytes) {
+        O.terminated[ag] = 0;
+        O.truncated[ag] = 0;
+      }
+      if (O.dist_goal) O.dist_goal[ag] = 0.f;
+      if (O.info_flags) O.info_flags[ag] = 0;
     }
     if (env_ok && t == 0)
       O.env_done[env] = (uint8_t)((term_all ? SWARM_ENV_TERMINATED : 0u) | (trunc_all ? SWARM_ENV_TRUNCATED : 0u) |
@@ -1193,7 +1218,7 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
         } else if (blk_rot) {
           pair_pass_block_fast<KS, 0>(pair_ring, N, t, px, py, pz, P.nb_keep, 0.f, nk, f2, s2);
         } else {
-          pair_pass_block<KS, 0>(ring, N, t, px, py, pz, true, P.nb_keep, 0.f, nk, s2, f2);
+          pair_pass_block<KS, 0>(ring, Ne, t, px, py, pz, true, P.nb_keep, 0.f, nk, s2, f2);
         }
         obstacle_pass<MSL, false>(obst4, Me, px, py, pz, false, 0.f, P.ob_keep, ok, c2);
       }
@@ -1206,6 +1231,7 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
   STAMP(6);
   // ---- state write-back
   const bool write_env = (mode == MODE_STEP) ? env_ok : sel;
+  const bool new_episode = (mode == MODE_STEP) ? do_reset : (mode == MODE_RESET && sel);
   if (is_agent) {
     if (mode == MODE_STEP) {
       bool new_act;
@@ -1232,6 +1258,20 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       gs[3 * N + 3 * t + 0] = vx; gs[3 * N + 3 * t + 1] = vy; gs[3 * N + 3 * t + 2] = vz;
       if (t == 0) { gs[6 * N + 0] = gx; gs[6 * N + 1] = gy; gs[6 * N + 2] = gz; }
     }
+  } else if (write_env && t < N) {
+    // a slot that is no drone of the (new) episode: zero state (never PAD_POS) and zero outputs
+    if (mode != MODE_OBSERVE) {
+      S.pos[ag * 3 + 0] = 0.f; S.pos[ag * 3 + 1] = 0.f; S.pos[ag * 3 + 2] = 0.f;
+      S.vel[ag * 3 + 0] = 0.f; S.vel[ag * 3 + 1] = 0.f; S.vel[ag * 3 + 2] = 0.f;
+      if (!packed_bytes) S.active[ag] = 0;
+      if (DYN == DYN_PHYS && new_episode) S.damping[ag] = 0.f;
+    }
+    if (mode != MODE_STEP && O.dist_goal) O.dist_goal[ag] = 0.f;
+    if (O.global_state) {
+      float* gs = O.global_state + env * (6LL * N + 3);
+      gs[3 * t + 0] = 0.f; gs[3 * t + 1] = 0.f; gs[3 * t + 2] = 0.f;
+      gs[3 * N + 3 * t + 0] = 0.f; gs[3 * N + 3 * t + 1] = 0.f; gs[3 * N + 3 * t + 2] = 0.f;
+    }
   }
   if (packed_bytes && env_ok) {  // wave-uniform (W64: the block is one env)
     const uint64_t mt = __ballot(term), mr = __ballot(trunc), ma = __ballot(new_act_out);
@@ -1244,7 +1284,6 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       *reinterpret_cast<uint32_t*>(base + env * 64 + 4 * (t & 15)) = word;
     }
   }
-  const bool new_episode = (mode == MODE_STEP) ? do_reset : (mode == MODE_RESET && sel);
   if (env_ok && t == 0) {
     if (mode == MODE_STEP) S.step_count[env] = do_reset ? 0 : new_step;
     else if (mode == MODE_RESET && sel) S.step_count[env] = 0;
@@ -1286,7 +1325,7 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
       for (int s = 0; s < KS - 1; ++s) {
         if (s < K) {
           float f0 = 0.f, f1 = 0.f, f2 = 0.f, f3 = 0.f;
-          if (wj[s] < N) {
+          if (wj[s] < Ne) {
             const float4 q = lds_f4(ring + wj[s]);
             f0 = q.x - px; f1 = q.y - py; f2 = q.z - pz; f3 = wd[s];
           }
@@ -1314,10 +1353,17 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
     }
   };
 
+  // the row of a slot that is no drone: zeros (the staged region is stored whole, so it must not
+  // keep stale LDS)
+  auto zero_row = [&](float* row) {
+    for (int c = 0; c < D; ++c) row[c] = 0.f;
+  };
+
   if ((mode != MODE_STEP && env_mask != nullptr) || (LM != 2 && P.obs_direct)) {
     // masked reset/observe (off the hot path), and small multi-team launches (latency-bound: the
     // LDS round trip and barriers of the staging lengthen every wave): rows straight to memory
     if (is_agent && sel) write_row(O.obs + (size_t)ag * D);
+    else if (sel && t < N) zero_row(O.obs + (size_t)ag * D);
   } else {
     // chunks of CH rows staged in LDS, then 16-B coalesced stores of the contiguous block region
     long long nvalid = P.E - env0;
@@ -1329,6 +1375,7 @@ swarm_kernel(const KParams P, const swarm_state_t S, const float* __restrict__ a
     float* dst0 = O.obs + env0 * N * D;
     for (int c = 0; c < G * N; c += CH) {  // block-uniform trip count
       if (is_agent && row_id >= c && row_id < c + CH) write_row(stage + (size_t)(row_id - c) * D);
+      else if (env_ok && t < N && row_id >= c && row_id < c + CH) zero_row(stage + (size_t)(row_id - c) * D);
       __syncthreads();
       const int nrow = rows - c < CH ? rows - c : CH;
       if (nrow > 0) {
@@ -4943,10 +4990,21 @@ __global__ void __launch_bounds__(256) env_cfg_set_kernel(const EnvCfgBase B, co
   c.s_phys_obst = s_threshold_dev((float)(orad + B.drone_contact_radius));
   c.max_steps = ov.max_steps ? ov.max_steps[e] : B.max_steps;
   c.num_obstacles = clamp_obstacles(ov.num_obstacles ? ov.num_obstacles[e] : B.M, B.M);
-  c.reserved = 0;
+  c.num_drones = 0;  // every slot (swarm_env_cfg_set_drones sets a count)
   c.max_speed_d = vmax;
   c.world_size = ws;
   out[e] = c;
+}
+
+// one thread per env: the drone count of the masked envs' records, nothing else of them
+__global__ void __launch_bounds__(256) env_cfg_set_drones_kernel(int E, int N, const int32_t* __restrict__ drones,
+                                                                 const uint8_t* __restrict__ env_mask,
+                                                                 swarm_env_cfg_t* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  if (env_mask != nullptr && env_mask[e] == 0) return;
+  const int n = drones ? drones[e] : N;
+  out[e].num_drones = n < 1 ? 1 : (n > N ? N : n);
 }
 
 }  // namespace
@@ -5154,6 +5212,20 @@ int swarm_env_cfg_set(const swarm_params_t* p, const swarm_env_overrides_t* ov, 
   b.drone_contact_radius = p->drone_contact_radius;
   hipLaunchKernelGGL(env_cfg_set_kernel, dim3((kp.E + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, b, *ov,
                      env_mask, cfg);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(SWARM_EHIP, "kernel launch: %s", hipGetErrorString(e));
+  return SWARM_OK;
+}
+
+int swarm_env_cfg_set_drones(const swarm_params_t* p, const int32_t* drones, const uint8_t* env_mask,
+                             swarm_env_cfg_t* cfg, void* hip_stream) {
+  KParams kp;
+  const int rc = build_kparams(p, &kp, nullptr);
+  if (rc) return rc;
+  if (kp.E == 0) return SWARM_OK;
+  if (!cfg) return fail(SWARM_ENULL, "env_cfg is NULL");
+  hipLaunchKernelGGL(env_cfg_set_drones_kernel, dim3((kp.E + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream,
+                     kp.E, kp.N, drones, env_mask, cfg);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(SWARM_EHIP, "kernel launch: %s", hipGetErrorString(e));
   return SWARM_OK;

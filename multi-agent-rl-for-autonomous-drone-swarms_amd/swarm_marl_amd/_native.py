@@ -60,6 +60,7 @@ CRITIC_MAX_IN = 1539
 EVAL_LIVE = 1
 EVAL_COLLIDED = 2
 EVAL_STEP_FUSED = 1
+EVAL_SLOT_COUNTS = 2
 EVAL_RECORD = 9
 EVAL_SEGMENTS = 64
 PPO_MAX_ACT = 6
@@ -76,7 +77,7 @@ EXPORTED_SYMBOLS = (
     "swarm_attn_policy_packed_bytes", "swarm_attn_policy_pack", "swarm_attn_policy_forward",
     "swarm_attn_policy_last_error",
     "swarm_eval_begin", "swarm_eval_update", "swarm_eval_single_update", "swarm_eval_last_error",
-    "swarm_env_cfg_set",
+    "swarm_env_cfg_set", "swarm_env_cfg_set_drones",
     "swarm_value_packed_bytes", "swarm_value_pack", "swarm_value_forward", "swarm_gae_agent", "swarm_value_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
@@ -144,7 +145,7 @@ class SwarmEnvCfg(ctypes.Structure):
     _fields_ = [(name, ctypes.c_float) for name in
                 ("half_w", "neg_half_w", "width_w", "dt", "max_speed", "max_accel", "s_vmax", "s_obst",
                  "s_phys_obst")] + [("max_steps", ctypes.c_int32), ("num_obstacles", ctypes.c_int32),
-                                    ("reserved", ctypes.c_int32), ("max_speed_d", ctypes.c_double),
+                                    ("num_drones", ctypes.c_int32), ("max_speed_d", ctypes.c_double),
                                     ("world_size", ctypes.c_double)]
 
 
@@ -284,6 +285,9 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     lib.swarm_eval_last_error.argtypes = []
     lib.swarm_env_cfg_set.restype = ctypes.c_int
     lib.swarm_env_cfg_set.argtypes = [P, ctypes.POINTER(SwarmEnvOverrides), vp, vp, vp]
+    if path is None or hasattr(lib, "swarm_env_cfg_set_drones"):  # (a library given by path may predate it)
+        lib.swarm_env_cfg_set_drones.restype = ctypes.c_int
+        lib.swarm_env_cfg_set_drones.argtypes = [P, vp, vp, vp, vp]
     if path is None or all(hasattr(lib, name) for name in ROLLOUT_SYMBOLS):
         lib.swarm_critic_packed_bytes.restype = ctypes.c_longlong
         lib.swarm_critic_packed_bytes.argtypes = [ctypes.c_int, ctypes.c_int]

@@ -5,15 +5,20 @@ an `env_config` (num_drones, num_obstacles, max_steps, world_size) trained for
 `train_iterations` with `seed = base_seed + stage_index`; the YAML also states promotion
 criteria over a rolling window of episodes (min success rate, min collision-free rate, max mean
 time to goal; `promotion_window_episodes`), which the reference script records but does not
-enforce.  Here a stage is a VecSwarm of E envs built from that env_config (stages change N and
-M, i.e. the tensor shapes, so each stage is its own batch) with an EvalTracker; the window
-metrics come from the device eval records and `advance()` moves on by iteration count, or by
-the criteria when asked to.
+enforce.  `CurriculumRunner` runs one stage at a time: a VecSwarm of E envs built from the
+stage's env_config with an EvalTracker; the window metrics come from the device eval records
+and `advance()` moves on by iteration count, or by the criteria when asked to.
 
-Stages that share N (stages 1-2 of curriculum_v1 are both N = 3) can also run side by side in ONE
-batch: `mixed_stage_batch` gives each env its stage's num_obstacles / max_steps / world_size as
-per-env parameters (swarm_env_cfg_t), so a curriculum can keep a replay fraction of earlier
-stages without a second launch.
+Stages can also run side by side in ONE batch, because every stage parameter is a per-env value
+(swarm_env_cfg_t) — the drone count included.  `mixed_size_batch` builds a batch of
+max(num_drones) slots and max(num_obstacles) obstacle slots per env and gives each env its
+stage's num_drones / num_obstacles / max_steps / world_size: env e behaves exactly like an env
+of a batch built from its stage's env_config, and the slots beyond its drone count do not exist
+(zero observation rows, never active, so `valid` drops them from every loss).  A curriculum can
+so keep a replay share of earlier stages, train one policy on several swarm sizes at once (the
+observation width does not depend on N), and promote envs one at a time: `assign_stage` moves
+the masked envs to another stage at their next episode end, with no rebuild.
+`mixed_stage_batch` is the older form for stages that share num_drones.
 """
 from __future__ import annotations
 
@@ -87,6 +92,75 @@ def mixed_stage_batch(cfg: dict, stage_of_env, *, base_seed: int = 0, seed: int 
                    seed=int(base_seed if seed is None else seed), **vec_kw)
     vec.set_env_config(**over)
     return vec, over
+
+
+def _stage_overrides(env_cfgs: dict, stages, with_drones: bool) -> dict:
+    from .envs.common import DroneEnvConfig
+    defaults = DroneEnvConfig()
+    over = {}
+    for k in STAGE_PARAMS:
+        vals = [env_cfgs[int(i)].get(k, getattr(defaults, k)) for i in stages]
+        over[k] = np.asarray(vals, dtype=np.int32 if k in ("max_steps", "num_obstacles") else np.float64)
+    if with_drones:
+        over["num_drones"] = np.asarray([int(env_cfgs[int(i)].get("num_drones", 3)) for i in stages], dtype=np.int32)
+    return over
+
+
+def _checked_stages(cfg: dict, stage_of_env) -> tuple[np.ndarray, dict]:
+    stages = np.asarray(stage_of_env, dtype=np.int64)
+    if stages.ndim != 1 or len(stages) == 0:
+        raise ValueError("stage_of_env must be a non-empty 1-D sequence of stage indices")
+    used = sorted(set(int(i) for i in stages))
+    if used[0] < 0 or used[-1] >= len(cfg["stages"]):
+        raise ValueError(f"stage index out of range [0, {len(cfg['stages'])})")
+    return stages, used
+
+
+def mixed_size_batch(cfg: dict, stage_of_env, *, base_seed: int = 0, seed: int | None = None, device=None,
+                     **vec_kw):
+    """One VecSwarm whose env e runs stage stage_of_env[e]'s env_config; the stages may differ in
+    num_drones as well as in STAGE_PARAMS (and in nothing else).  The batch has max(num_drones)
+    slots and max(num_obstacles) obstacle slots per env; each env gets its stage's values as
+    per-env parameters, and comes back reset.  Returns (vec, overrides): `overrides` maps each
+    parameter (num_drones included) to its [E] numpy array."""
+    stages, used = _checked_stages(cfg, stage_of_env)
+    env_cfgs = {i: stage_env_config(cfg, i, base_seed) for i in used}
+    rest = [{k: v for k, v in c.items() if k not in STAGE_PARAMS + ("seed", "num_drones")} for c in env_cfgs.values()]
+    if any(r != rest[0] for r in rest):
+        raise ValueError("stages differ in fields other than num_drones, " + ", ".join(STAGE_PARAMS))
+    from .envs.common import DroneEnvConfig
+    batch = dict(rest[0])
+    batch["num_obstacles"] = max(int(c.get("num_obstacles", DroneEnvConfig.num_obstacles)) for c in env_cfgs.values())
+    batch["num_drones"] = max(int(c.get("num_drones", 3)) for c in env_cfgs.values())
+    over = _stage_overrides(env_cfgs, stages, True)
+    vec = VecSwarm(len(stages), batch, device=device, auto_reset=True,
+                   seed=int(base_seed if seed is None else seed), **vec_kw)
+    # current records, then a reset: the reset draws, activates and observes with each env's count
+    vec.set_env_config(**over)
+    vec.reset()
+    return vec, over
+
+
+def assign_stage(vec: VecSwarm, cfg: dict, env_mask, stage_index: int, next_episode: bool = True, *,
+                 base_seed: int = 0) -> dict:
+    """Move the masked envs ([E] bool / uint8 device tensor; None = all) of a `mixed_size_batch`
+    to stage `stage_index`: its num_drones and STAGE_PARAMS become those envs' next-episode
+    parameters, in force from each env's next reset (auto or explicit) — per-env promotion with
+    no rebuild.  next_episode=False writes the current parameters instead; reset those envs
+    before their next step.  The stage must fit the batch (num_drones and num_obstacles within
+    its slots).  Returns the stage's values."""
+    if not 0 <= int(stage_index) < len(cfg["stages"]):
+        raise ValueError(f"stage index out of range [0, {len(cfg['stages'])})")
+    env_cfg = stage_env_config(cfg, int(stage_index), base_seed)
+    over = {k: v[0].item() for k, v in _stage_overrides({0: env_cfg}, [0], True).items()}
+    if over["num_drones"] > vec.num_drones:
+        raise ValueError(f"stage {stage_index} has {over['num_drones']} drones, the batch {vec.num_drones} slots")
+    if over["num_obstacles"] > int(vec.cfg.num_obstacles):
+        raise ValueError(f"stage {stage_index} has {over['num_obstacles']} obstacles, the batch "
+                         f"{int(vec.cfg.num_obstacles)} slots")
+    # (the first next-episode write starts every env's next record as a copy of its current one)
+    vec.set_env_config(env_mask=env_mask, next_episode=next_episode, **over)
+    return over
 
 
 def criteria_met(metrics: dict, criteria: dict | None) -> bool:

@@ -59,7 +59,11 @@ class EvalTracker:
     episode that ends) — the same records, bit for bit (tests/test_gpu_eval.py) — and update()
     launches nothing: it counts the update (the record's update index).  Every step of the
     VecSwarm then updates, so call update() after every step (as without fusion); `detach()`
-    ends the fusion."""
+    ends the fusion.
+
+    A batch with per-env drone counts (`set_env_config(num_drones=...)`) is tracked unfused: an
+    episode's path efficiency is the mean over the drones the env has in that episode (the slots
+    stepped on the episode's first step), so begin the tracker at episode starts."""
 
     def __init__(self, vec: VecSwarm, capacity: int = 65536, fused="auto"):
         if vec.info_flags is None:
@@ -193,6 +197,10 @@ class EvalTracker:
 
     def _group_c(self, g: int) -> nat.SwarmEval:
         self._c.update_index = self.updates
+        if not self.fused and getattr(self.vec, "has_drone_counts", False):
+            # per-env drone counts (set_env_config(num_drones=...)): path efficiency averages
+            # over the slots that exist in the episode
+            self._c.flags = nat.EVAL_SLOT_COUNTS
         if self.vec.groups == 1:
             return self._c
         lo = self.vec.group_slices[g][0]

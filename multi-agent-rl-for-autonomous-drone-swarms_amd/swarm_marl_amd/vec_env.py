@@ -208,6 +208,7 @@ class VecSwarm:
                      if self.persistent else None)
         # per-env parameter records ([E, 64] bytes of swarm_env_cfg_t; set_env_config)
         self.env_cfg = self.env_cfg_next = None
+        self.has_drone_counts = False  # set_env_config(num_drones=...) was used
         # ---- outputs (persistent buffers)
         outs = [("obs", (e, n, d), f32), ("reward", (e, n), f32)]
         if with_infos:
@@ -495,7 +496,7 @@ class VecSwarm:
 
     # ------------------------------------------------------------------ per-env parameters
     def set_env_config(self, *, env_mask: torch.Tensor | None = None, next_episode: bool = False,
-                       **values) -> None:
+                       num_drones=None, **values) -> None:
         """Per-env parameters (curriculum stages and domain randomisation as
         per-env tensors).  `values` maps any of world_size, dt, max_speed, max_accel,
         obstacle_radius (float), max_steps, num_obstacles (int, 0..num_obstacles of the batch) to a
@@ -506,11 +507,23 @@ class VecSwarm:
         a curriculum mix keeps them across resets).  next_episode=True sets the parameters each
         env's NEXT episode starts with: every reset (auto or explicit) copies them in — the hook
         for per-episode randomisation (domain_randomization.py).  The step then runs the generic
-        kernel."""
+        kernel.
+
+        num_drones (scalar or [E] int, 1..num_drones of the batch; device values are clamped):
+        the env's drone count n_e (swarm_env_cfg_set_drones).  The env then behaves exactly like
+        an env of a batch built with num_drones = n_e; slots >= n_e do not exist and every step
+        and reset writes zeros for them (obs row, reward, flags, active, state).  A call that
+        does not name num_drones keeps every env's count, current and next.  With
+        next_episode=True a count takes effect at the env's next reset (it may grow or shrink).
+        With next_episode=False reset the masked envs (or `set_state` them) before their next
+        step: the state of a slot that starts to exist holds no drone until then."""
         unknown = set(values) - set(nat.ENV_OVERRIDE_FIELDS)
         if unknown:
             raise ValueError(f"unknown per-env parameters {sorted(unknown)}; "
-                             f"supported: {nat.ENV_OVERRIDE_FIELDS}")
+                             f"supported: {nat.ENV_OVERRIDE_FIELDS + ('num_drones',)}")
+        counts = None
+        if num_drones is not None:
+            counts = self._drone_counts(num_drones)
         if self.dynamics == "physics" and values.get("dt") is not None:
             raise ValueError("per-env dt applies to the kinematic integrator only (physics substeps are "
                              "uniform)")
@@ -532,7 +545,55 @@ class VecSwarm:
             rebind = True
         if rebind:
             self._bind()
-        self._env_cfg_write(self.env_cfg_next if next_episode else self.env_cfg, values, env_mask)
+        dst = self.env_cfg_next if next_episode else self.env_cfg
+        if counts is not None and not self.has_drone_counts:
+            # first use: every record's count field holds a count from here on (0 meant "all N")
+            self.has_drone_counts = True
+            for rec in (self.env_cfg, self.env_cfg_next):
+                if rec is not None:
+                    self._env_cfg_drones(rec, None, None)
+        # swarm_env_cfg_set rewrites whole records: the counts are carried over on the device
+        # (the kernels move next-episode counts into the current records, so no host copy of
+        # them would stay true)
+        kept = self._count_view(dst).clone() if self.has_drone_counts else None
+        self._env_cfg_write(dst, values, env_mask)
+        if kept is not None:
+            self._count_view(dst).copy_(kept)
+        if counts is not None:
+            self._env_cfg_drones(dst, counts, env_mask)
+
+    @staticmethod
+    def _count_view(rec: torch.Tensor) -> torch.Tensor:
+        """[E] int32 view of the records' drone-count field (swarm_env_cfg_t.num_drones)."""
+        return rec.view(torch.int32)[:, nat.SwarmEnvCfg.num_drones.offset // 4]
+
+    def _drone_counts(self, num_drones) -> torch.Tensor:
+        """num_drones as a contiguous [E] int32 device tensor; host values are range-checked."""
+        e, n = self.num_envs, self.num_drones
+        if not (isinstance(num_drones, torch.Tensor) and num_drones.is_cuda):
+            host = torch.as_tensor(num_drones)
+            if host.is_floating_point() or host.is_complex():
+                raise ValueError("num_drones must be integers")
+            if host.numel() and (int(host.min()) < 1 or int(host.max()) > n):
+                raise ValueError(f"num_drones must be in [1, {n}] (the batch's slots per env), got "
+                                 f"{int(host.min())}..{int(host.max())}")
+            num_drones = host
+        t = num_drones.to(device=self.device, dtype=torch.int32)
+        if t.dim() == 0:
+            t = t.expand(e)
+        if tuple(t.shape) != (e,):
+            raise ValueError(f"num_drones: expected a scalar or shape ({e},), got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def _env_cfg_drones(self, dst: torch.Tensor, counts: torch.Tensor | None, env_mask) -> None:
+        mp = self._mask_ptr(env_mask)
+        for g, (lo, _) in enumerate(self.group_slices):
+            rc = self.lib.swarm_env_cfg_set_drones(ctypes.byref(self._gparams[g]),
+                                                   None if counts is None else counts.data_ptr() + lo * 4,
+                                                   None if mp is None else mp + lo,
+                                                   dst.data_ptr() + lo * nat.ENV_CFG_BYTES, self._stream())
+            nat.check(rc, self.lib)
+        self._keep_counts = counts  # the launches read it asynchronously
 
     def _env_cfg_write(self, dst: torch.Tensor, values: dict, env_mask) -> None:
         e = self.num_envs
@@ -565,7 +626,8 @@ class VecSwarm:
         self._keep_cfg = keep  # the launches read them asynchronously
 
     def env_config(self, next_episode: bool = False) -> dict[str, torch.Tensor] | None:
-        """Per-env parameters as [E] tensors (views of the records), or None if unset."""
+        """Per-env parameters as [E] tensors (views of the records), or None if unset.
+        num_drones reads 0 (= every slot) in records that were never given a count."""
         rec = self.env_cfg_next if next_episode else self.env_cfg
         if rec is None:
             return None
@@ -573,7 +635,8 @@ class VecSwarm:
         i = rec.view(torch.int32)
         d = rec.view(torch.float64)
         return dict(world_size=d[:, 7], dt=f[:, 3], max_speed=d[:, 6], max_accel=f[:, 5],
-                    max_steps=i[:, 9], num_obstacles=i[:, 10], half_w=f[:, 0], s_obst=f[:, 7])
+                    max_steps=i[:, 9], num_obstacles=i[:, 10], half_w=f[:, 0], s_obst=f[:, 7],
+                    num_drones=i[:, 11])
 
     def state_dict(self) -> dict[str, torch.Tensor]:
         return dict(pos=self.pos, vel=self.vel, goal=self.goal, obstacles=self.obstacles,
