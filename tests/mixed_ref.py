@@ -80,9 +80,11 @@ def _cfg(base: dict, over: dict | None, e: int, n_e: int) -> dict:
 
 
 def step(base: dict, cur: dict | None, counts, state: dict, actions, *, nxt: dict | None = None,
-         counts_next=None, auto_reset: bool = True, seed: int = 0, env_offset: int = 0, physics: bool = False):
+         counts_next=None, auto_reset: bool = True, seed: int = 0, env_offset: int = 0, physics: bool = False,
+         action_mask=None):
     """One step of every env.  Returns (new_state, out, new_cur, new_counts): the overrides and
-    counts in force after the step (the next-episode ones for envs that reset)."""
+    counts in force after the step (the next-episode ones for envs that reset).  action_mask
+    [E, N] (True = the drone sent an action): env e sees its first n_e entries."""
     e_n, n = state["pos"].shape[:2]
     cnt = counts_of(counts, e_n, n)
     cnt_next = None if counts_next is None else counts_of(counts_next, e_n, n)
@@ -95,12 +97,13 @@ def step(base: dict, cur: dict | None, counts, state: dict, actions, *, nxt: dic
             new_cur[k] = np.array([eco.env_cfg(base, cur, e)[k] for e in range(e_n)])
     outs = []
     actions = np.asarray(actions)
+    am = None if action_mask is None else np.asarray(action_mask, bool)
     for e in range(e_n):
         n_e = int(cnt[e])
         cfg_e = _cfg(base, cur, e, n_e)
         st_e = _slice(state, e, n_e, cfg_e["num_obstacles"])
-        ns, o = so.step(cfg_e, st_e, actions[e:e + 1, :n_e], auto_reset=False, seed=seed,
-                        env_offset=env_offset + e, physics=physics)
+        ns, o = so.step(cfg_e, st_e, actions[e:e + 1, :n_e], None if am is None else am[e:e + 1, :n_e],
+                        auto_reset=False, seed=seed, env_offset=env_offset + e, physics=physics)
         done = bool(o["term_all"][0] or o["trunc_all"][0])
         out = {k: pad_agents(o[k], n) for k in AGENT_OUT}
         out["term_all"], out["trunc_all"] = o["term_all"], o["trunc_all"]
@@ -150,6 +153,33 @@ def reset(base: dict, cur: dict | None, counts, state: dict, *, nxt: dict | None
         out["dist_goal"][e] = pad_agents(ro["dist_goal"], n)[0]
         out["global_state"][e] = pad_global_state(ro["global_state"], n)[0]
     return new_state, out, new_cnt
+
+
+def observe(base: dict, cur: dict | None, counts, state: dict, env_mask=None, physics: bool = False,
+            out: dict | None = None) -> dict:
+    """swarm_observe of the masked envs (all if None): obs [E, N, D], dist_goal [E, N] and
+    global_state [E, 6N + 3] of the current state, each env observed on its own with
+    num_drones = n_e (so.observe / so.global_state) and padded with zeros.  Rows of envs outside
+    the mask are left as they are in `out` (a dict of the three arrays, written in place), NaN
+    when no `out` is given.  The state is not touched."""
+    e_n, n = state["pos"].shape[:2]
+    cnt = counts_of(counts, e_n, n)
+    mask = np.ones(e_n, bool) if env_mask is None else np.asarray(env_mask, bool)
+    d = so.obs_dim(base)
+    if out is None:
+        out = dict(obs=np.full((e_n, n, d), np.nan, f32), dist_goal=np.full((e_n, n), np.nan, f32),
+                   global_state=np.full((e_n, 6 * n + 3), np.nan, f32))
+    for e in range(e_n):
+        if not mask[e]:
+            continue
+        n_e = int(cnt[e])
+        cfg_e = _cfg(base, cur, e, n_e)
+        st = _slice(state, e, n_e, cfg_e["num_obstacles"])
+        obs = so.observe(cfg_e, st["pos"], st["vel"], st["goal"], st["obst"], physics=physics)
+        out["obs"][e] = pad_agents(obs, n)[0]
+        out["dist_goal"][e] = pad_agents(so.norm1d(st["goal"][:, None, :] - st["pos"]), n)[0]
+        out["global_state"][e] = pad_global_state(so.global_state(st["pos"], st["vel"], st["goal"]), n)[0]
+    return out
 
 
 def info_flags(out: dict) -> np.ndarray:

@@ -130,6 +130,80 @@ def test_mixed_counts_equal_single_env_batches():
     assert switched.all()
 
 
+@pytest.mark.parametrize("physics", [False, True])
+def test_masked_step_with_uniform_counts_equals_oracle(physics):
+    """With every n_e = N the reference's masked step is so.step(cfg, st, a, am, ...) bit for bit
+    (no auto-reset: down to n_active == 0 in the kinematic mode)."""
+    from oracle import swarm_oracle as so
+    n, e = 5, 4
+    base = so.make_cfg(num_drones=n, num_obstacles=4, max_steps=4)
+    st_a, _ = so.reset_device(base, so.empty_state(base, e), seed=6, physics=physics)
+    st_b = {k: v.copy() for k, v in st_a.items()}
+    rng = np.random.default_rng(1)
+    absent = 0
+    for t in range(6):
+        a = rng.uniform(-2, 2, (e, n, 3)).astype(np.float32)
+        am = rng.uniform(size=(e, n)) > 0.3
+        absent += int((~am).sum())
+        st_a, out_a = so.step(base, st_a, a, am, auto_reset=False, seed=6, physics=physics)
+        st_b, out_b, _, cnt = mr.step(base, {}, np.full(e, n), st_b, a, auto_reset=False, seed=6, physics=physics,
+                                      action_mask=am)
+        assert set(out_a) == set(out_b) and np.array_equal(cnt, np.full(e, n))
+        for k in out_a:
+            assert np.array_equal(out_a[k], out_b[k]), (t, k)
+        for k in st_a:
+            assert np.array_equal(st_a[k], st_b[k]), (t, k)
+    assert absent > 0 and not st_a["active"].any()
+    # the mask matters: the unmasked step of the same state differs
+    st0, _ = so.reset_device(base, so.empty_state(base, e), seed=6, physics=physics)
+    a = rng.uniform(-2, 2, (e, n, 3)).astype(np.float32)
+    am = np.zeros((e, n), bool)
+    s1, _, _, _ = mr.step(base, {}, None, st0, a, auto_reset=False, seed=6, physics=physics, action_mask=am)
+    s2, _, _, _ = mr.step(base, {}, None, st0, a, auto_reset=False, seed=6, physics=physics)
+    assert not np.array_equal(s1["vel"], s2["vel"])
+
+
+@pytest.mark.parametrize("physics", [False, True])
+def test_observe_reference(physics):
+    """mr.observe: so.observe / norm1d / so.global_state for uniform counts; for mixed counts every
+    env observed alone with num_drones = n_e, zeros in the slots that do not exist; envs outside
+    the mask untouched; the state is not changed."""
+    from oracle import swarm_oracle as so
+    n, m, e = 5, 4, 4
+    base = so.make_cfg(num_drones=n, num_obstacles=m, max_steps=9)
+    st, _ = so.reset_device(base, so.empty_state(base, e), seed=8, physics=physics)
+    rng = np.random.default_rng(5)
+    st["vel"] = rng.uniform(-6, 6, st["vel"].shape).astype(np.float32)  # some above max_speed (physics clamps)
+    got = mr.observe(base, {}, None, st, physics=physics)
+    assert np.array_equal(got["obs"], so.observe(base, st["pos"], st["vel"], st["goal"], st["obst"], physics=physics))
+    assert np.array_equal(got["dist_goal"], so.norm1d(st["goal"][:, None, :] - st["pos"]))
+    assert np.array_equal(got["global_state"], so.global_state(st["pos"], st["vel"], st["goal"]))
+    counts = np.array([3, 5, 1, 2])
+    ov = dict(num_obstacles=np.array([4, 0, 2, 1], np.int32))
+    keep = {k: v.copy() for k, v in st.items()}
+    mask = np.array([True, True, False, True])
+    got = mr.observe(base, ov, counts, st, env_mask=mask, physics=physics)
+    for k in st:
+        assert np.array_equal(st[k], keep[k]), k
+    for i, c in enumerate(counts):
+        if not mask[i]:
+            assert all(np.isnan(got[k][i]).all() for k in got)
+            continue
+        cfg = dict(base, num_drones=int(c), num_obstacles=int(ov["num_obstacles"][i]))
+        p, v, g, o = st["pos"][i:i + 1, :c], st["vel"][i:i + 1, :c], st["goal"][i:i + 1], \
+            st["obst"][i:i + 1, :cfg["num_obstacles"]]
+        assert np.array_equal(got["obs"][i, :c], so.observe(cfg, p, v, g, o, physics=physics)[0])
+        assert not got["obs"][i, c:].any() and not got["dist_goal"][i, c:].any()
+        assert np.array_equal(got["dist_goal"][i, :c], so.norm1d(g[:, None, :] - p)[0])
+        assert np.array_equal(got["global_state"][i], mr.pad_global_state(so.global_state(p, v, g), n)[0])
+        if c - 1 < base["neighbor_k"]:  # spare neighbour slots are zero
+            assert not got["obs"][i, :c, 9 + 4 * (c - 1):9 + 4 * base["neighbor_k"]].any()
+    # `out` given: rows outside the mask keep what they held
+    out = {k: np.full_like(v, 7.0) for k, v in got.items()}
+    mr.observe(base, ov, counts, st, env_mask=mask, physics=physics, out=out)
+    assert all((out[k][2] == 7.0).all() and np.array_equal(out[k][mask], got[k][mask]) for k in out)
+
+
 def test_set_drones_argument_errors(nat, lib):
     """swarm_env_cfg_set_drones validates before any launch (no GPU is touched)."""
     p0 = _params(nat, lib, num_envs=0)
