@@ -27,25 +27,16 @@
 #include <string.h>
 
 #include "swarm_mi355x.h"
+#include "swarm_nn.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef const __attribute__((address_space(4))) float* cfloat_p;  // constant address space: scalar loads
 
-constexpr int H = SWARM_POLICY_HIDDEN;  // 256
 constexpr int EM = SWARM_ATTN_EMBED;    // 32
 constexpr int KS1 = 4;                  // layer-1 k-steps: [s 32 | own, obst, 1: <= 30, padded to 32]
-constexpr int OB = H / 32;              // 8 out blocks of 32
-constexpr int KS2 = H / 16;             // 16 k-steps over the hidden dim
-constexpr int FRAG = 1024;              // bytes of one 64-lane x 16-B fragment block
 
 // f32 front-end block of the bf16 blob (float offsets)
 constexpr int FE_OWN_W = 0, FE_OWN_B = FE_OWN_W + EM * 9, FE_NB_W = FE_OWN_B + EM, FE_NB_B = FE_NB_W + EM * 4,
@@ -90,51 +81,13 @@ struct F32Layout {
   }
 };
 
-// hidden unit carried by k-step `ks` (of 16) of an accumulator-chained operand, lane half h, element j
-__host__ __device__ inline int chained_k(int ks, int h, int j) {
-  return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-}
 // s component carried by layer-1 fragment column k < 32 (k-step k >> 4, lane half (k >> 3) & 1)
 __host__ __device__ inline int s_of_col(int k) { return 16 * ((k >> 3) & 1) + 8 * (k >> 4) + (k & 7); }
 
-uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 
-// 8 accumulator values -> bf16 fragment, relu'd after the conversion (swarm_policy.hip's pack8)
-__device__ __forceinline__ bf16x8 pack8(const f32x16& a, int s, bool act) {
-  u32x4 w;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bf16x2 p = __builtin_convertvector((f32x2){a[8 * s + 2 * q], a[8 * s + 2 * q + 1]}, bf16x2);
-    s16x2 v = __builtin_bit_cast(s16x2, p);
-    if (act) v = __builtin_elementwise_max(v, (s16x2){0, 0});
-    w[q] = __builtin_bit_cast(unsigned, v);
-  }
-  return __builtin_bit_cast(bf16x8, w);
-}
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2));
-}
-
-// Philox4x32-10 and the Box-Muller normals of swarm_policy_forward (tests/policy_ref.py
-// sample_noise64): the same operations in the same order, so the draws are bit-identical
-__device__ __forceinline__ void philox(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
 }
 
 struct FwdArgs {
@@ -146,22 +99,6 @@ struct FwdArgs {
   int k, ms, out;
   uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
 };
-
-__device__ __forceinline__ void normals(const FwdArgs& A, long long r, int ad, float (&z)[6]) {
-  uint32_t c[4] = {(uint32_t)r, (uint32_t)((unsigned long long)r >> 32), A.ctr_lo, A.ctr_hi};
-  philox(c, A.seed_lo, A.seed_hi);
-  uint32_t c2[4] = {(uint32_t)r, (uint32_t)((unsigned long long)r >> 32) ^ 0x80000000u, A.ctr_lo, A.ctr_hi};
-  if (ad > 2) philox(c2, A.seed_lo, A.seed_hi);
-  const uint32_t uu[8] = {c[0], c[1], c[2], c[3], c2[0], c2[1], c2[2], c2[3]};
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const float u1 = ((float)(uu[2 * p] >> 8) + 0.5f) * 0x1p-24f;
-    const float u2 = (float)(uu[2 * p + 1] >> 8) * 0x1p-24f;
-    const float rr = sqrtf(-2.f * logf(u1));
-    z[2 * p] = rr * cosf(6.28318530717958647692f * u2);
-    z[2 * p + 1] = rr * sinf(6.28318530717958647692f * u2);
-  }
-}
 
 // ---------------------------------------------------------------- bf16 kernel
 constexpr int LDS_W2 = 0;                    // LDS image: W2 fragments, then the layer-1 fragments
@@ -553,33 +490,18 @@ __global__ void __launch_bounds__(256) attn_policy_f32(const FwdArgs A) {
 
 constexpr int BF16_WAVES = 8;  // one workgroup per CU (the LDS image), two waves per SIMD
 
-thread_local char g_aerr[256] = "";
-int afail(int code, const char* msg) {
-  strncpy(g_aerr, msg, sizeof(g_aerr) - 1);
-  return code;
-}
-
-int num_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-  }
-  return cus;
-}
+thread_local UnitError g_err;
 
 int check_dims(int k, int ms, int out_dim, int precision) {
   if (k < 1 || k > SWARM_ATTN_MAX_K)
-    return afail(SWARM_ELIMIT, "neighbor_k out of range: the attention actor takes 1..16 neighbour slots (SWARM_ATTN_MAX_K)");
+    return g_err.fail(SWARM_ELIMIT, "neighbor_k out of range: the attention actor takes 1..16 neighbour slots (SWARM_ATTN_MAX_K)");
   if (ms < 0 || ms > SWARM_ATTN_MAX_MS)
-    return afail(SWARM_ELIMIT, "sensed_obstacles out of range: the attention actor takes 0..5 (SWARM_ATTN_MAX_MS)");
+    return g_err.fail(SWARM_ELIMIT, "sensed_obstacles out of range: the attention actor takes 0..5 (SWARM_ATTN_MAX_MS)");
   if (out_dim < 2 || out_dim > SWARM_POLICY_MAX_OUT || (out_dim & 1))
-    return afail(SWARM_ELIMIT, "out_dim must be even, 2..12 (SWARM_POLICY_MAX_OUT)");
+    return g_err.fail(SWARM_ELIMIT, "out_dim must be even, 2..12 (SWARM_POLICY_MAX_OUT)");
   if (precision == SWARM_POLICY_F32X3)
-    return afail(SWARM_ELIMIT, "the attention actor has no f32x3 path: SWARM_POLICY_BF16 or SWARM_POLICY_F32");
-  if (precision != SWARM_POLICY_BF16 && precision != SWARM_POLICY_F32) return afail(SWARM_EINVAL, "unknown precision");
+    return g_err.fail(SWARM_ELIMIT, "the attention actor has no f32x3 path: SWARM_POLICY_BF16 or SWARM_POLICY_F32");
+  if (precision != SWARM_POLICY_BF16 && precision != SWARM_POLICY_F32) return g_err.fail(SWARM_EINVAL, "unknown precision");
   return SWARM_OK;
 }
 
@@ -587,7 +509,7 @@ int check_dims(int k, int ms, int out_dim, int precision) {
 
 extern "C" {
 
-const char* swarm_attn_policy_last_error(void) { return g_aerr; }
+const char* swarm_attn_policy_last_error(void) { return g_err.msg; }
 
 long long swarm_attn_policy_packed_bytes(int neighbor_k, int sensed_obstacles, int out_dim, int precision) {
   const int rc = check_dims(neighbor_k, sensed_obstacles, out_dim, precision);
@@ -600,10 +522,10 @@ int swarm_attn_policy_pack(int neighbor_k, int sensed_obstacles, int out_dim, in
                            const swarm_attn_weights_t* w, void* host_out) {
   const long long nb = swarm_attn_policy_packed_bytes(neighbor_k, sensed_obstacles, out_dim, precision);
   if (nb < 0) return (int)nb;
-  if (!w || !host_out) return afail(SWARM_ENULL, "null weights / output pointer");
+  if (!w || !host_out) return g_err.fail(SWARM_ENULL, "null weights / output pointer");
   if (!w->neighbor_w || !w->neighbor_b || !w->own_w || !w->own_b || !w->in_proj_w || !w->in_proj_b ||
       !w->out_proj_w || !w->out_proj_b || !w->w1 || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3)
-    return afail(SWARM_ENULL, "null weight pointer");
+    return g_err.fail(SWARM_ENULL, "null weight pointer");
   memset(host_out, 0, (size_t)nb);
   const int ms = sensed_obstacles, in1 = 9 + EM + 4 * ms;
   if (precision == SWARM_POLICY_F32) {
@@ -706,16 +628,16 @@ int swarm_attn_policy_pack(int neighbor_k, int sensed_obstacles, int out_dim, in
 int swarm_attn_policy_forward(const swarm_attn_policy_t* p, const float* obs, long long rows, float* logits,
                               float* actions, int action_mode, unsigned long long seed, unsigned long long counter,
                               void* hip_stream) {
-  if (!p || !p->weights) return afail(SWARM_ENULL, "policy/weights is NULL");
+  if (!p || !p->weights) return g_err.fail(SWARM_ENULL, "policy/weights is NULL");
   const int rc = check_dims(p->neighbor_k, p->sensed_obstacles, p->out_dim, p->precision);
   if (rc != SWARM_OK) return rc;
-  if (rows < 0) return afail(SWARM_EINVAL, "rows < 0");
+  if (rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
   if (rows == 0) return SWARM_OK;
-  if (!obs) return afail(SWARM_ENULL, "obs is NULL");
-  if (!logits && !actions) return afail(SWARM_ENULL, "need logits and/or actions");
+  if (!obs) return g_err.fail(SWARM_ENULL, "obs is NULL");
+  if (!logits && !actions) return g_err.fail(SWARM_ENULL, "need logits and/or actions");
   if (action_mode != SWARM_POLICY_ACT_MEAN && action_mode != SWARM_POLICY_ACT_SAMPLE)
-    return afail(SWARM_EINVAL, "unknown action_mode");
-  if (((uintptr_t)p->weights) % 16) return afail(SWARM_EINVAL, "weights must be 16-B aligned");
+    return g_err.fail(SWARM_EINVAL, "unknown action_mode");
+  if (((uintptr_t)p->weights) % 16) return g_err.fail(SWARM_EINVAL, "weights must be 16-B aligned");
   FwdArgs a;
   a.w = p->weights;
   a.obs = obs;
@@ -731,27 +653,21 @@ int swarm_attn_policy_forward(const swarm_attn_policy_t* p, const float* obs, lo
   a.ctr_hi = (uint32_t)(counter >> 32);
   hipStream_t s = (hipStream_t)hip_stream;
   const bool sample = action_mode == SWARM_POLICY_ACT_SAMPLE;
-  const int cus = num_cus();
   if (p->precision == SWARM_POLICY_BF16) {
     const int lds = LDS_BYTES;
     auto fn = sample ? attn_policy_bf16<BF16_WAVES, SWARM_POLICY_ACT_SAMPLE>
                      : attn_policy_bf16<BF16_WAVES, SWARM_POLICY_ACT_MEAN>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
         hipSuccess)
-      return afail(SWARM_EHIP, "hipFuncSetAttribute failed");
-    const long long need = ((rows + 63) / 64 + BF16_WAVES - 1) / BF16_WAVES;
-    const int grid = (int)(need < cus ? need : cus);
+      return g_err.fail(SWARM_EHIP, "hipFuncSetAttribute failed");
+    const int grid = grid_for(((rows + 63) / 64 + BF16_WAVES - 1) / BF16_WAVES, 1);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * BF16_WAVES), lds, s, a);
   } else {
     auto fn = sample ? attn_policy_f32<SWARM_POLICY_ACT_SAMPLE> : attn_policy_f32<SWARM_POLICY_ACT_MEAN>;
-    const long long need = (rows + RB - 1) / RB;
-    const long long cap = 4LL * cus;
-    const int grid = (int)(need < cap ? need : cap);
+    const int grid = grid_for((rows + RB - 1) / RB, 4);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, s, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return afail(SWARM_EHIP, hipGetErrorString(e));
-  return SWARM_OK;
+  return g_err.launch_status();
 }
 
 }  // extern "C"

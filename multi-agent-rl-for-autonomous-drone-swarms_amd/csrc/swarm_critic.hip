@@ -36,22 +36,12 @@
 #include <string.h>
 
 #include "swarm_mi355x.h"
+#include "swarm_nn.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-constexpr int H = SWARM_POLICY_HIDDEN;  // 256
-constexpr int OB = H / 32;              // 8 out blocks of 32
-constexpr int KS2 = H / 16;             // 16 k-steps over the hidden dim
-constexpr int FRAG = 1024;              // bytes of one 64-lane x 16-B fragment block
 constexpr int KC = 2;                   // layer-1 k-steps per chunk
 constexpr int WCHUNK = KC * OB * FRAG;  // 16 KB: one W1 chunk; one W2 chunk (1 out block x 16 k-steps) too
 static_assert(WCHUNK == KS2 * FRAG, "W1 and W2 chunks share the LDS buffers");
@@ -87,24 +77,6 @@ struct F32Layout {
   }
 };
 
-// hidden unit carried by k-step `ks` (of 16) of an accumulator-chained operand, lane half h, element j
-// (swarm_policy.hip: the accumulator's register order)
-inline int chained_k(int ks, int h, int j) { return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
-
-uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-float bf16_to_f32(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
 struct CriticArgs {
   const void* w;     // packed blob (device)
   const float* gs;   // [rows, in]
@@ -112,19 +84,6 @@ struct CriticArgs {
   long long rows;
   int in;
 };
-
-// 8 accumulator values -> relu'd bf16 fragment (swarm_policy.hip pack8: relu as a packed i16 max)
-__device__ __forceinline__ bf16x8 pack8_relu(const f32x16& a, int s) {
-  u32x4 w;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bf16x2 p = __builtin_convertvector((f32x2){a[8 * s + 2 * q], a[8 * s + 2 * q + 1]}, bf16x2);
-    s16x2 v = __builtin_bit_cast(s16x2, p);
-    v = __builtin_elementwise_max(v, (s16x2){0, 0});
-    w[q] = __builtin_bit_cast(unsigned, v);
-  }
-  return __builtin_bit_cast(bf16x8, w);
-}
 
 // one thread's share of a 16-KB weight chunk: four 16-B pieces, BF16_THREADS apart (named members,
 // not an array: an array the optimizer cannot split is moved to LDS or scratch)
@@ -228,8 +187,8 @@ critic_mlp_bf16(const CriticArgs A) {
     bf16x8 h1[KS2];
 #pragma unroll
     for (int ob = 0; ob < OB; ++ob) {
-      h1[2 * ob] = pack8_relu(acc[ob], 0);
-      h1[2 * ob + 1] = pack8_relu(acc[ob], 1);
+      h1[2 * ob] = pack8(acc[ob], 0, true);
+      h1[2 * ob + 1] = pack8(acc[ob], 1, true);
     }
     // ---- layer 2 (256 x 256, relu), one out block per chunk, fused with layer 3 (1 x 256)
     float v = 0.f;
@@ -367,7 +326,7 @@ __global__ void __launch_bounds__(H) critic_mlp_f32(const CriticArgs A) {
   }
 }
 
-// ---------------------------------------------------------------- log-prob, GAE
+// ---------------------------------------------------------------- log-prob
 __global__ void __launch_bounds__(256) gaussian_logp_kernel(const float* __restrict__ logits,
                                                             const float* __restrict__ actions, long long rows, int adim,
                                                             float* __restrict__ logp) {
@@ -384,97 +343,29 @@ __global__ void __launch_bounds__(256) gaussian_logp_kernel(const float* __restr
   }
 }
 
-struct GaeArgs {
-  const float* reward;
-  const float* value;
-  const uint8_t* terminated;
-  const uint8_t* truncated;
-  const uint8_t* env_done;
-  const uint8_t* valid;
-  float* advantage;
-  float* value_target;
-  int T, E, N;
-  float gamma, lam;
-};
-
-// one thread per (env, agent), t from T - 1 down to 0: the header's loop, operation for operation
-__global__ void __launch_bounds__(256) gae_kernel(const GaeArgs A) {
-  const long long en = (long long)A.E * A.N;
-  const float gl = A.gamma * A.lam;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < en; i += (long long)gridDim.x * blockDim.x) {
-    const long long e = i / A.N;
-    float carry = 0.f;
-    for (int t = A.T - 1; t >= 0; --t) {
-      const long long at = (long long)t * en + i;
-      if (!A.valid[at]) {
-        A.advantage[at] = 0.f;
-        A.value_target[at] = 0.f;
-        carry = 0.f;
-        continue;
-      }
-      const bool done = (A.terminated[at] | A.truncated[at]) != 0 ||
-                        (A.env_done[(long long)t * A.E + e] & (SWARM_ENV_TERMINATED | SWARM_ENV_TRUNCATED)) != 0;
-      const float v = A.value[(long long)t * A.E + e];
-      const float nv = done ? 0.f : A.value[(long long)(t + 1) * A.E + e];
-      const float prev = done ? 0.f : carry;
-      const float delta = (A.reward[at] + A.gamma * nv) - v;
-      carry = delta + gl * prev;
-      A.advantage[at] = carry;
-      A.value_target[at] = carry + v;
-    }
-  }
-}
-
-thread_local char g_cerr[256] = "";
-int cfail(int code, const char* msg) {
-  strncpy(g_cerr, msg, sizeof(g_cerr) - 1);
-  return code;
-}
-
-int device_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-  }
-  return cus;
-}
-
-int grid_for(long long blocks_needed, int per_cu) {
-  const long long cap = (long long)device_cus() * per_cu;
-  const long long g = blocks_needed < cap ? blocks_needed : cap;
-  return g < 1 ? 1 : (int)g;
-}
-
-int launch_status() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return cfail(SWARM_EHIP, hipGetErrorString(e));
-  return SWARM_OK;
-}
+thread_local UnitError g_err;
 
 }  // namespace
 
 extern "C" {
 
-const char* swarm_critic_last_error(void) { return g_cerr; }
+const char* swarm_critic_last_error(void) { return g_err.msg; }
 
 long long swarm_critic_packed_bytes(int in_dim, int precision) {
   if (in_dim < 1 || in_dim > SWARM_CRITIC_MAX_IN)
-    return cfail(SWARM_ELIMIT, "critic in_dim out of range [1, 1539]"), (long long)SWARM_ELIMIT;
+    return g_err.fail(SWARM_ELIMIT, "critic in_dim out of range [1, 1539]"), (long long)SWARM_ELIMIT;
   if (precision == SWARM_POLICY_BF16) return (long long)Bf16Layout(in_dim).total;
   if (precision == SWARM_POLICY_F32) return (long long)F32Layout(in_dim).total * 4;
   if (precision == SWARM_POLICY_F32X3)
-    return cfail(SWARM_ELIMIT, "the critic has no f32x3 path (bf16 or f32)"), (long long)SWARM_ELIMIT;
-  return cfail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
+    return g_err.fail(SWARM_ELIMIT, "the critic has no f32x3 path (bf16 or f32)"), (long long)SWARM_ELIMIT;
+  return g_err.fail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
 }
 
 int swarm_critic_pack(int in_dim, int precision, const float* w1, const float* b1, const float* w2, const float* b2,
                       const float* w3, const float* b3, void* host_out) {
   const long long nb = swarm_critic_packed_bytes(in_dim, precision);
   if (nb < 0) return (int)nb;
-  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return cfail(SWARM_ENULL, "null weight pointer");
+  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return g_err.fail(SWARM_ENULL, "null weight pointer");
   memset(host_out, 0, (size_t)nb);
   if (precision == SWARM_POLICY_BF16) {
     const Bf16Layout L(in_dim);
@@ -515,13 +406,13 @@ int swarm_critic_pack(int in_dim, int precision, const float* w1, const float* b
 }
 
 int swarm_critic_forward(const swarm_critic_t* c, const float* gs, long long rows, float* value, void* hip_stream) {
-  if (!c || !c->weights) return cfail(SWARM_ENULL, "critic/weights is NULL");
+  if (!c || !c->weights) return g_err.fail(SWARM_ENULL, "critic/weights is NULL");
   const long long nb = swarm_critic_packed_bytes(c->in_dim, c->precision);
   if (nb < 0) return (int)nb;
-  if (rows < 0) return cfail(SWARM_EINVAL, "rows < 0");
+  if (rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
   if (rows == 0) return SWARM_OK;
-  if (!gs || !value) return cfail(SWARM_ENULL, "gs/value is NULL");
-  if (((uintptr_t)c->weights) % 16) return cfail(SWARM_EINVAL, "weights must be 16-B aligned");
+  if (!gs || !value) return g_err.fail(SWARM_ENULL, "gs/value is NULL");
+  if (((uintptr_t)c->weights) % 16) return g_err.fail(SWARM_EINVAL, "weights must be 16-B aligned");
   CriticArgs a;
   a.w = c->weights;
   a.gs = gs;
@@ -534,44 +425,25 @@ int swarm_critic_forward(const swarm_critic_t* c, const float* gs, long long row
     hipLaunchKernelGGL(critic_mlp_bf16, dim3(grid_for((rows + TILE - 1) / TILE, 16)), dim3(BF16_THREADS), 0, s, a);
   else
     hipLaunchKernelGGL(critic_mlp_f32, dim3(grid_for((rows + F32_ROWS - 1) / F32_ROWS, 32)), dim3(H), 0, s, a);
-  return launch_status();
+  return g_err.launch_status();
 }
 
 int swarm_gaussian_logp(const float* logits, const float* actions, long long rows, int adim, float* logp,
                         void* hip_stream) {
-  if (rows < 0 || adim < 1) return cfail(SWARM_EINVAL, "rows < 0 or adim < 1");
+  if (rows < 0 || adim < 1) return g_err.fail(SWARM_EINVAL, "rows < 0 or adim < 1");
   if (rows == 0) return SWARM_OK;
-  if (!logits || !actions || !logp) return cfail(SWARM_ENULL, "logits/actions/logp is NULL");
+  if (!logits || !actions || !logp) return g_err.fail(SWARM_ENULL, "logits/actions/logp is NULL");
   // the per-CU cap (32 blocks, here and in swarm_gae) is mirrored by tests/test_gpu_rollout.py
   hipLaunchKernelGGL(gaussian_logp_kernel, dim3(grid_for((rows + 255) / 256, 32)), dim3(256), 0, (hipStream_t)hip_stream,
                      logits, actions, rows, adim, logp);
-  return launch_status();
+  return g_err.launch_status();
 }
 
 int swarm_gae(const float* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated,
               const uint8_t* env_done, const uint8_t* valid, int T, int E, int N, float gamma, float lam,
               float* advantage, float* value_target, void* hip_stream) {
-  if (T < 0 || E < 0 || N < 0) return cfail(SWARM_EINVAL, "T, E, N must be >= 0");
-  if (T == 0 || E == 0 || N == 0) return SWARM_OK;
-  if (!reward || !value || !terminated || !truncated || !env_done || !valid || !advantage || !value_target)
-    return cfail(SWARM_ENULL, "a GAE buffer is NULL");
-  GaeArgs a;
-  a.reward = reward;
-  a.value = value;
-  a.terminated = terminated;
-  a.truncated = truncated;
-  a.env_done = env_done;
-  a.valid = valid;
-  a.advantage = advantage;
-  a.value_target = value_target;
-  a.T = T;
-  a.E = E;
-  a.N = N;
-  a.gamma = gamma;
-  a.lam = lam;
-  const long long en = (long long)E * N;
-  hipLaunchKernelGGL(gae_kernel, dim3(grid_for((en + 255) / 256, 32)), dim3(256), 0, (hipStream_t)hip_stream, a);
-  return launch_status();
+  return gae_launch<false>(reward, value, terminated, truncated, env_done, valid, T, E, N, gamma, lam, advantage,
+                           value_target, hip_stream, g_err);
 }
 
 }  // extern "C"

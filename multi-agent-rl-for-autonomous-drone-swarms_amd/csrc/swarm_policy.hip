@@ -28,21 +28,16 @@
 #include <string.h>
 
 #include "swarm_mi355x.h"
+#include "swarm_nn.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int H = SWARM_POLICY_HIDDEN;  // 256
 constexpr int KP1 = 48;                 // bf16 layer-1 K (obs dim + bias column, padded)
 constexpr int KS1 = KP1 / 16;           // 3 k-steps
-constexpr int OB = H / 32;              // 8 out blocks of 32 (bf16 path)
-constexpr int KS2 = H / 16;             // 16 k-steps over the hidden dim
-constexpr int FRAG = 1024;              // bytes of one 64-lane x 16-B fragment block
 
 // ---------------------------------------------------------------- packed blob layouts
 // bf16: [W1F 8x3 blocks][W2F 8x16 blocks][W3F 16 k-steps x 2*out lanes x 16 B][b2 256 f32][b3 32 f32]
@@ -73,10 +68,6 @@ struct F32Layout {
   }
 };
 
-// hidden unit carried by k-step `ks` (of 16) of an accumulator-chained operand, lane half h, element j
-__host__ __device__ inline int chained_k(int ks, int h, int j) {
-  return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-}
 // f32 16x16x4 chaining: k-step q (of 64) of lane quarter g -> hidden unit
 __host__ __device__ inline int chained_k_f32(int q, int g) { return (q >> 2) * 16 + 4 * g + (q & 3); }
 
@@ -115,49 +106,8 @@ float f16_to_f32(uint16_t h) {
   return f;
 }
 
-uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
 // ---------------------------------------------------------------- bf16 kernel
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
-
-// 8 accumulator values -> bf16 fragment, relu'd after the conversion: round-to-nearest keeps the
-// sign, so relu(bf16(x)) == bf16(relu(x)), and a bf16 with the sign bit set is a negative int16:
-// one v_pk_max_i16 with 0 relus two values (an f32 relu costs a canonicalising v_max plus the max
-// on MFMA outputs: 4x the instructions).
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-__device__ __forceinline__ bf16x8 pack8(const f32x16& a, int s, bool act) {
-  u32x4 w;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bf16x2 p = __builtin_convertvector((f32x2){a[8 * s + 2 * q], a[8 * s + 2 * q + 1]}, bf16x2);  // v_cvt_pk_bf16_f32
-    s16x2 v = __builtin_bit_cast(s16x2, p);
-    if (act) v = __builtin_elementwise_max(v, (s16x2){0, 0});  // v_pk_max_i16
-    w[q] = __builtin_bit_cast(unsigned, v);
-  }
-  return __builtin_bit_cast(bf16x8, w);
-}
-
-// Philox4x32-10 (same constants as the env's device reset)
-__device__ __forceinline__ void philox(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
 
 struct FwdArgs {
   const void* w;        // packed blob (device)
@@ -332,22 +282,7 @@ policy_mlp_bf16(const FwdArgs A) {
         const int ad = out / 2;
         if (h == 0 && valid[u]) {
           float z[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          if constexpr (MODE == SWARM_POLICY_ACT_SAMPLE) {  // Box-Muller normals from Philox(seed; row, counter)
-            const long long r = row[u];
-            uint32_t c[4] = {(uint32_t)r, (uint32_t)((unsigned long long)r >> 32), A.ctr_lo, A.ctr_hi};
-            philox(c, A.seed_lo, A.seed_hi);
-            uint32_t c2[4] = {(uint32_t)r, (uint32_t)((unsigned long long)r >> 32) ^ 0x80000000u, A.ctr_lo, A.ctr_hi};
-            if (ad > 2) philox(c2, A.seed_lo, A.seed_hi);
-            const uint32_t uu[8] = {c[0], c[1], c[2], c[3], c2[0], c2[1], c2[2], c2[3]};
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-              const float u1 = ((float)(uu[2 * p] >> 8) + 0.5f) * 0x1p-24f;
-              const float u2 = (float)(uu[2 * p + 1] >> 8) * 0x1p-24f;
-              const float rr = sqrtf(-2.f * logf(u1));
-              z[2 * p] = rr * cosf(6.28318530717958647692f * u2);
-              z[2 * p + 1] = rr * sinf(6.28318530717958647692f * u2);
-            }
-          }
+          if constexpr (MODE == SWARM_POLICY_ACT_SAMPLE) SWARM_NORMALS(A, row[u], ad, z)  // in place: see swarm_nn.h
 #pragma unroll
           for (int k = 0; k < 6; ++k) {
             if (k < ad) {
@@ -932,45 +867,31 @@ constexpr int X3_WAVES = 4;
 // (the one-wave pipelined kernel; same outputs bit for bit)
 constexpr int X3L_WAVES = 8;
 
-thread_local char g_perr[256] = "";
-int pfail(int code, const char* msg) {
-  strncpy(g_perr, msg, sizeof(g_perr) - 1);
-  return code;
-}
+thread_local UnitError g_err;
 
-int grid_for(int waves_per_block, long long tiles) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-  }
-  long long need = (tiles + waves_per_block - 1) / waves_per_block;
-  long long g = need < cus ? need : cus;
-  return g < 1 ? 1 : (int)g;
-}
+// workgroups for `tiles` wave tiles: one workgroup per CU at most (the LDS blob)
+int tile_grid(int waves_per_block, long long tiles) { return grid_for((tiles + waves_per_block - 1) / waves_per_block, 1); }
 
 }  // namespace
 
 extern "C" {
 
-const char* swarm_policy_last_error(void) { return g_perr; }
+const char* swarm_policy_last_error(void) { return g_err.msg; }
 
 long long swarm_policy_packed_bytes(int in_dim, int out_dim, int precision) {
   if (in_dim < 1 || in_dim > SWARM_POLICY_MAX_IN || out_dim < 2 || out_dim > SWARM_POLICY_MAX_OUT || (out_dim & 1))
-    return pfail(SWARM_ELIMIT, "policy dims out of range"), (long long)SWARM_ELIMIT;
+    return g_err.fail(SWARM_ELIMIT, "policy dims out of range"), (long long)SWARM_ELIMIT;
   if (precision == SWARM_POLICY_BF16) return (long long)Bf16Layout(out_dim).total;
   if (precision == SWARM_POLICY_F32X3) return 2 * (long long)Bf16Layout(out_dim).total;  // hi blob, lo blob
   if (precision == SWARM_POLICY_F32) return (long long)F32Layout(in_dim).total * 4;
-  return pfail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
+  return g_err.fail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
 }
 
 int swarm_policy_pack(int in_dim, int out_dim, int precision, const float* w1, const float* b1, const float* w2,
                       const float* b2, const float* w3, const float* b3, void* host_out) {
   const long long nb = swarm_policy_packed_bytes(in_dim, out_dim, precision);
   if (nb < 0) return (int)nb;
-  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return pfail(SWARM_ENULL, "null weight pointer");
+  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return g_err.fail(SWARM_ENULL, "null weight pointer");
   memset(host_out, 0, (size_t)nb);
   if (precision == SWARM_POLICY_F32X3) {
     // the bf16 blob's fragment order twice, f16 elements: hi = f16(v), then lo = f16((v - hi) 2^11)
@@ -1056,17 +977,17 @@ int swarm_policy_pack(int in_dim, int out_dim, int precision, const float* w1, c
 
 int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long rows, float* logits, float* actions,
                          int action_mode, unsigned long long seed, unsigned long long counter, void* hip_stream) {
-  if (!p || !p->weights) return pfail(SWARM_ENULL, "policy/weights is NULL");
+  if (!p || !p->weights) return g_err.fail(SWARM_ENULL, "policy/weights is NULL");
   if (swarm_policy_packed_bytes(p->in_dim, p->out_dim, p->precision) < 0) return SWARM_ELIMIT;
-  if (rows < 0) return pfail(SWARM_EINVAL, "rows < 0");
+  if (rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
   if (rows == 0) return SWARM_OK;
-  if (!obs) return pfail(SWARM_ENULL, "obs is NULL");
-  if (!logits && !actions) return pfail(SWARM_ENULL, "need logits and/or actions");
+  if (!obs) return g_err.fail(SWARM_ENULL, "obs is NULL");
+  if (!logits && !actions) return g_err.fail(SWARM_ENULL, "need logits and/or actions");
   if (action_mode != SWARM_POLICY_ACT_MEAN && action_mode != SWARM_POLICY_ACT_SAMPLE)
-    return pfail(SWARM_EINVAL, "unknown action_mode");
+    return g_err.fail(SWARM_EINVAL, "unknown action_mode");
   if (action_mode == SWARM_POLICY_ACT_SAMPLE && p->precision != SWARM_POLICY_BF16)
-    return pfail(SWARM_EINVAL, "sampled actions are implemented on the bf16 path");
-  if (((uintptr_t)p->weights) % 16) return pfail(SWARM_EINVAL, "weights must be 16-B aligned");
+    return g_err.fail(SWARM_EINVAL, "sampled actions are implemented on the bf16 path");
+  if (((uintptr_t)p->weights) % 16) return g_err.fail(SWARM_EINVAL, "weights must be 16-B aligned");
   FwdArgs a;
   a.w = p->weights;
   a.obs = obs;
@@ -1091,8 +1012,8 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
                           : policy_mlp_bf16<BF16_WAVES_T, SWARM_POLICY_ACT_MEAN, BF16_TILES>);
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
         hipSuccess)
-      return pfail(SWARM_EHIP, "hipFuncSetAttribute failed");
-    const int grid = grid_for(BF16_WAVES_T, ((rows + 31) / 32 + BF16_TILES - 1) / BF16_TILES);
+      return g_err.fail(SWARM_EHIP, "hipFuncSetAttribute failed");
+    const int grid = tile_grid(BF16_WAVES_T, ((rows + 31) / 32 + BF16_TILES - 1) / BF16_TILES);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * BF16_WAVES_T), lds, s, a);
   } else if (p->precision == SWARM_POLICY_F32X3) {
     const int lds = (int)Bf16Layout(p->out_dim).total;
@@ -1104,16 +1025,14 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
     const int waves = lean ? X3L_WAVES : X3_WAVES;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
         hipSuccess)
-      return pfail(SWARM_EHIP, "hipFuncSetAttribute failed");
-    const int grid = grid_for(waves, (rows + 31) / 32);
+      return g_err.fail(SWARM_EHIP, "hipFuncSetAttribute failed");
+    const int grid = tile_grid(waves, (rows + 31) / 32);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), lds, s, a);
   } else {
-    const int grid = grid_for(F32_WAVES, (rows + 15) / 16) * 2;
+    const int grid = tile_grid(F32_WAVES, (rows + 15) / 16) * 2;
     hipLaunchKernelGGL(policy_mlp_f32<F32_WAVES>, dim3(grid), dim3(64 * F32_WAVES), 0, s, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pfail(SWARM_EHIP, hipGetErrorString(e));
-  return SWARM_OK;
+  return g_err.launch_status();
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "swarm_mi355x.h"
+#include "swarm_nn.h"
 
 #pragma clang fp contract(off)
 
@@ -282,17 +283,7 @@ __global__ void __launch_bounds__(64) ppo_final(const double* __restrict__ work,
   }
 }
 
-thread_local char g_perr[256] = "";
-int pfail(int code, const char* msg) {
-  strncpy(g_perr, msg, sizeof(g_perr) - 1);
-  return code;
-}
-
-int launch_status() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return pfail(SWARM_EHIP, hipGetErrorString(e));
-  return SWARM_OK;
-}
+thread_local UnitError g_err;
 
 template <int A>
 void launch_loss(const swarm_ppo_args_t& a, long long env_rows, long long tiles, int G, int blocks, hipStream_t s) {
@@ -303,15 +294,15 @@ void launch_loss(const swarm_ppo_args_t& a, long long env_rows, long long tiles,
 
 extern "C" {
 
-const char* swarm_ppo_last_error(void) { return g_perr; }
+const char* swarm_ppo_last_error(void) { return g_err.msg; }
 
 int swarm_masked_moments(const float* x, const uint8_t* valid, long long rows, void* workspace, double* out,
                          void* hip_stream) {
-  if (rows < 0) return pfail(SWARM_EINVAL, "rows < 0");
+  if (rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
   if (rows == 0) return SWARM_OK;
-  if (!x || !valid || !workspace || !out) return pfail(SWARM_ENULL, "x/valid/workspace/out is NULL");
+  if (!x || !valid || !workspace || !out) return g_err.fail(SWARM_ENULL, "x/valid/workspace/out is NULL");
   if (((uintptr_t)workspace) % 8 || ((uintptr_t)out) % 8 || ((uintptr_t)x) % 4)
-    return pfail(SWARM_EINVAL, "workspace/out must be 8-B aligned, x 4-B aligned");
+    return g_err.fail(SWARM_EINVAL, "workspace/out must be 8-B aligned, x 4-B aligned");
   // 4 rows per thread and pass where the pointers allow 16-B / 4-B vector loads
   const bool vec = ((uintptr_t)x) % 16 == 0 && ((uintptr_t)valid) % 4 == 0;
   const long long per_block = (long long)THREADS * (vec ? 16 : 4);
@@ -324,25 +315,25 @@ int swarm_masked_moments(const float* x, const uint8_t* valid, long long rows, v
   else
     hipLaunchKernelGGL(moments_kernel<false>, dim3((int)nb), dim3(THREADS), 0, s, x, valid, rows, work);
   hipLaunchKernelGGL(moments_final, dim3(1), dim3(64), 0, s, (const double*)work, (int)nb, out);
-  return launch_status();
+  return g_err.launch_status();
 }
 
 int swarm_ppo_loss(const swarm_ppo_args_t* args, void* hip_stream) {
-  if (!args) return pfail(SWARM_ENULL, "args is NULL");
+  if (!args) return g_err.fail(SWARM_ENULL, "args is NULL");
   const swarm_ppo_args_t& a = *args;
-  if (a.rows < 0) return pfail(SWARM_EINVAL, "rows < 0");
-  if (a.act_dim < 1 || a.act_dim > SWARM_PPO_MAX_ACT) return pfail(SWARM_ELIMIT, "act_dim out of range [1, 6]");
+  if (a.rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
+  if (a.act_dim < 1 || a.act_dim > SWARM_PPO_MAX_ACT) return g_err.fail(SWARM_ELIMIT, "act_dim out of range [1, 6]");
   if (a.num_agents < 1 || a.num_agents > SWARM_PPO_MAX_AGENTS)
-    return pfail(SWARM_ELIMIT, "num_agents out of range [1, 256]");
-  if (a.rows % a.num_agents) return pfail(SWARM_EINVAL, "rows is not a multiple of num_agents");
+    return g_err.fail(SWARM_ELIMIT, "num_agents out of range [1, 256]");
+  if (a.rows % a.num_agents) return g_err.fail(SWARM_EINVAL, "rows is not a multiple of num_agents");
   if (a.rows == 0) return SWARM_OK;
   if (!a.logits || !a.behaviour_logits || !a.actions || !a.logp || !a.advantage || !a.value_target || !a.value ||
       !a.valid || !a.adv_moments || !a.valid_moments || !a.grad_logits || !a.grad_value || !a.stats || !a.workspace)
-    return pfail(SWARM_ENULL, "a PPO buffer is NULL");
+    return g_err.fail(SWARM_ENULL, "a PPO buffer is NULL");
   if (((uintptr_t)a.logits) % 8 || ((uintptr_t)a.behaviour_logits) % 8 || ((uintptr_t)a.grad_logits) % 8 ||
       ((uintptr_t)a.workspace) % 8 || ((uintptr_t)a.stats) % 8 || ((uintptr_t)a.adv_moments) % 8 ||
       ((uintptr_t)a.valid_moments) % 8)
-    return pfail(SWARM_EINVAL, "logits, behaviour_logits, grad_logits, the moments, stats and workspace must be 8-B aligned");
+    return g_err.fail(SWARM_EINVAL, "logits, behaviour_logits, grad_logits, the moments, stats and workspace must be 8-B aligned");
   const int G = THREADS / a.num_agents;  // >= 1: whole env-rows of a tile
   const long long env_rows = a.rows / a.num_agents;
   const long long tiles = (env_rows + G - 1) / G;
@@ -358,7 +349,7 @@ int swarm_ppo_loss(const swarm_ppo_args_t* args, void* hip_stream) {
   }
   const Coef c{a.clip_param, a.vf_clip_param, a.vf_loss_coeff, a.entropy_coeff, a.kl_coeff};
   hipLaunchKernelGGL(ppo_final, dim3(1), dim3(64), 0, s, (const double*)a.workspace, blocks, a.valid_moments, c, a.stats);
-  return launch_status();
+  return g_err.launch_status();
 }
 
 }  // extern "C"

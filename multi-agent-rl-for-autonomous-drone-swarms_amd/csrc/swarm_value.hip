@@ -32,24 +32,14 @@
 #include <string.h>
 
 #include "swarm_mi355x.h"
+#include "swarm_nn.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-constexpr int H = SWARM_POLICY_HIDDEN;  // 256
 constexpr int KP1 = 48;                 // layer-1 K (obs dim + bias column, padded)
 constexpr int KS1 = KP1 / 16;           // 3 k-steps
-constexpr int OB = H / 32;              // 8 out blocks of 32
-constexpr int KS2 = H / 16;             // 16 k-steps over the hidden dim
-constexpr int FRAG = 1024;              // bytes of one 64-lane x 16-B fragment block
 static_assert(SWARM_POLICY_MAX_IN + 1 <= KP1, "the bias column sits inside the padded K");
 
 // bf16 blob: [W1F 8 x 3 blocks][W2F 8 x 16 blocks][b2 256 f32][w3 256 f32, bf16-rounded][b3, 4 f32]
@@ -61,24 +51,6 @@ constexpr size_t L_B3 = L_W3 + H * 4;
 constexpr size_t L_TOTAL = L_B3 + 16;  // 157,712 B: one workgroup per CU (160 KiB of LDS)
 static_assert(L_TOTAL % 16 == 0 && L_TOTAL <= 160 * 1024, "the blob is staged whole, in 16-B pieces");
 
-// hidden unit carried by k-step `ks` (of 16) of an accumulator-chained operand, lane half h, element j
-// (swarm_policy.hip: the accumulator's register order)
-inline int chained_k(int ks, int h, int j) { return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
-
-uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-float bf16_to_f32(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
 struct ValueArgs {
   const void* w;     // packed blob (device)
   const float* obs;  // [rows, in]
@@ -86,20 +58,6 @@ struct ValueArgs {
   long long rows;
   int in;
 };
-
-// 8 accumulator values (sub-block s) -> relu'd bf16 pairs (swarm_policy.hip pack8: round to nearest
-// keeps the sign, so the relu is a packed i16 max with 0 after the conversion)
-__device__ __forceinline__ u32x4 pack8_relu(const f32x16& a, int s) {
-  u32x4 w;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const bf16x2 p = __builtin_convertvector((f32x2){a[8 * s + 2 * q], a[8 * s + 2 * q + 1]}, bf16x2);  // v_cvt_pk_bf16_f32
-    s16x2 v = __builtin_bit_cast(s16x2, p);
-    v = __builtin_elementwise_max(v, (s16x2){0, 0});  // v_pk_max_i16
-    w[q] = __builtin_bit_cast(unsigned, v);
-  }
-  return w;
-}
 
 // 8 waves per workgroup (one workgroup per CU: the LDS blob), one 32-row tile per wave: the actor's
 // measured choice; ~124 registers, two waves per SIMD.  Two tiles per wave (every
@@ -176,8 +134,8 @@ value_mlp_bf16(const ValueArgs A) {
 #pragma unroll
       for (int ks = 0; ks < KS1; ++ks)
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1f[(ob * KS1 + ks) * 64], xb[ks], acc, 0, 0, 0);
-      h1[2 * ob] = __builtin_bit_cast(bf16x8, pack8_relu(acc, 0));
-      h1[2 * ob + 1] = __builtin_bit_cast(bf16x8, pack8_relu(acc, 1));
+      h1[2 * ob] = pack8(acc, 0, true);
+      h1[2 * ob + 1] = pack8(acc, 1, true);
       __builtin_amdgcn_sched_barrier(0);  // keep each out block's fragment reads inside it
     }
     // ---- layer 2 (256 x 256, relu) fused with layer 3 (1 x 256): each out block's relu'd bf16
@@ -202,7 +160,7 @@ value_mlp_bf16(const ValueArgs A) {
       // pair widens to f32 with a shift and a mask
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const u32x4 p = pack8_relu(acc, s);
+        const u32x4 p = pack8_u32(acc, s, true);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           v = v + w3v[8 * s + 2 * q] * __uint_as_float(p[q] << 16);
@@ -218,100 +176,31 @@ value_mlp_bf16(const ValueArgs A) {
 
 constexpr int BF16_WAVES = 8;
 
-struct GaeArgs {
-  const float* reward;
-  const float* value;
-  const uint8_t* terminated;
-  const uint8_t* truncated;
-  const uint8_t* env_done;
-  const uint8_t* valid;
-  float* advantage;
-  float* value_target;
-  int T, E, N;
-  float gamma, lam;
-};
-
-// one thread per (env, agent), t from T - 1 down to 0: the header's loop, operation for operation
-__global__ void __launch_bounds__(256) gae_agent_kernel(const GaeArgs A) {
-  const long long en = (long long)A.E * A.N;
-  const float gl = A.gamma * A.lam;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < en; i += (long long)gridDim.x * blockDim.x) {
-    const long long e = i / A.N;
-    float carry = 0.f;
-    for (int t = A.T - 1; t >= 0; --t) {
-      const long long at = (long long)t * en + i;
-      if (!A.valid[at]) {
-        A.advantage[at] = 0.f;
-        A.value_target[at] = 0.f;
-        carry = 0.f;
-        continue;
-      }
-      const bool done = (A.terminated[at] | A.truncated[at]) != 0 ||
-                        (A.env_done[(long long)t * A.E + e] & (SWARM_ENV_TERMINATED | SWARM_ENV_TRUNCATED)) != 0;
-      const float v = A.value[at];
-      float nv = 0.f;
-      if (!done) nv = A.value[at + en];
-      const float prev = done ? 0.f : carry;
-      const float delta = (A.reward[at] + A.gamma * nv) - v;
-      carry = delta + gl * prev;
-      A.advantage[at] = carry;
-      A.value_target[at] = carry + v;
-    }
-  }
-}
-
-thread_local char g_verr[256] = "";
-int vfail(int code, const char* msg) {
-  strncpy(g_verr, msg, sizeof(g_verr) - 1);
-  return code;
-}
+thread_local UnitError g_err;
 // an error of the f32 path's swarm_critic_* call, under this unit's name
-int vcritic(int code) { return code < 0 ? vfail(code, swarm_critic_last_error()) : code; }
-
-int device_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-  }
-  return cus;
-}
-
-int grid_for(long long blocks_needed, int per_cu) {
-  const long long cap = (long long)device_cus() * per_cu;
-  const long long g = blocks_needed < cap ? blocks_needed : cap;
-  return g < 1 ? 1 : (int)g;
-}
-
-int launch_status() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return vfail(SWARM_EHIP, hipGetErrorString(e));
-  return SWARM_OK;
-}
+int vcritic(int code) { return code < 0 ? g_err.fail(code, swarm_critic_last_error()) : code; }
 
 }  // namespace
 
 extern "C" {
 
-const char* swarm_value_last_error(void) { return g_verr; }
+const char* swarm_value_last_error(void) { return g_err.msg; }
 
 long long swarm_value_packed_bytes(int in_dim, int precision) {
   if (in_dim < 1 || in_dim > SWARM_POLICY_MAX_IN)
-    return vfail(SWARM_ELIMIT, "value in_dim out of range [1, 47]"), (long long)SWARM_ELIMIT;
+    return g_err.fail(SWARM_ELIMIT, "value in_dim out of range [1, 47]"), (long long)SWARM_ELIMIT;
   if (precision == SWARM_POLICY_BF16) return (long long)L_TOTAL;
   if (precision == SWARM_POLICY_F32) return (long long)vcritic((int)swarm_critic_packed_bytes(in_dim, precision));
   if (precision == SWARM_POLICY_F32X3)
-    return vfail(SWARM_ELIMIT, "the per-agent critic has no f32x3 path (bf16 or f32)"), (long long)SWARM_ELIMIT;
-  return vfail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
+    return g_err.fail(SWARM_ELIMIT, "the per-agent critic has no f32x3 path (bf16 or f32)"), (long long)SWARM_ELIMIT;
+  return g_err.fail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
 }
 
 int swarm_value_pack(int in_dim, int precision, const float* w1, const float* b1, const float* w2, const float* b2,
                      const float* w3, const float* b3, void* host_out) {
   const long long nb = swarm_value_packed_bytes(in_dim, precision);
   if (nb < 0) return (int)nb;
-  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return vfail(SWARM_ENULL, "null weight pointer");
+  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return g_err.fail(SWARM_ENULL, "null weight pointer");
   if (precision == SWARM_POLICY_F32) return vcritic(swarm_critic_pack(in_dim, precision, w1, b1, w2, b2, w3, b3, host_out));
   memset(host_out, 0, (size_t)nb);
   unsigned char* base = static_cast<unsigned char*>(host_out);
@@ -337,13 +226,13 @@ int swarm_value_pack(int in_dim, int precision, const float* w1, const float* b1
 }
 
 int swarm_value_forward(const swarm_value_t* v, const float* obs, long long rows, float* value, void* hip_stream) {
-  if (!v || !v->weights) return vfail(SWARM_ENULL, "value/weights is NULL");
+  if (!v || !v->weights) return g_err.fail(SWARM_ENULL, "value/weights is NULL");
   const long long nb = swarm_value_packed_bytes(v->in_dim, v->precision);
   if (nb < 0) return (int)nb;
-  if (rows < 0) return vfail(SWARM_EINVAL, "rows < 0");
+  if (rows < 0) return g_err.fail(SWARM_EINVAL, "rows < 0");
   if (rows == 0) return SWARM_OK;
-  if (!obs || !value) return vfail(SWARM_ENULL, "obs/value is NULL");
-  if (((uintptr_t)v->weights) % 16) return vfail(SWARM_EINVAL, "weights must be 16-B aligned");
+  if (!obs || !value) return g_err.fail(SWARM_ENULL, "obs/value is NULL");
+  if (((uintptr_t)v->weights) % 16) return g_err.fail(SWARM_EINVAL, "weights must be 16-B aligned");
   if (v->precision == SWARM_POLICY_F32) {
     swarm_critic_t c;
     c.in_dim = v->in_dim;
@@ -360,39 +249,19 @@ int swarm_value_forward(const swarm_value_t* v, const float* obs, long long rows
   auto fn = v->in_dim == 37 ? value_mlp_bf16<BF16_WAVES, 37> : value_mlp_bf16<BF16_WAVES>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L_TOTAL) !=
       hipSuccess)
-    return vfail(SWARM_EHIP, "hipFuncSetAttribute failed");
+    return g_err.fail(SWARM_EHIP, "hipFuncSetAttribute failed");
   // one workgroup per CU at most (8 x 32 rows per pass of one): mirrored by tests/test_gpu_value.py
   const long long tiles = (rows + 31) / 32;
   hipLaunchKernelGGL(fn, dim3(grid_for((tiles + BF16_WAVES - 1) / BF16_WAVES, 1)), dim3(64 * BF16_WAVES), (int)L_TOTAL,
                      (hipStream_t)hip_stream, a);
-  return launch_status();
+  return g_err.launch_status();
 }
 
 int swarm_gae_agent(const float* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated,
                     const uint8_t* env_done, const uint8_t* valid, int T, int E, int N, float gamma, float lam,
                     float* advantage, float* value_target, void* hip_stream) {
-  if (T < 0 || E < 0 || N < 0) return vfail(SWARM_EINVAL, "T, E, N must be >= 0");
-  if (T == 0 || E == 0 || N == 0) return SWARM_OK;
-  if (!reward || !value || !terminated || !truncated || !env_done || !valid || !advantage || !value_target)
-    return vfail(SWARM_ENULL, "a GAE buffer is NULL");
-  GaeArgs a;
-  a.reward = reward;
-  a.value = value;
-  a.terminated = terminated;
-  a.truncated = truncated;
-  a.env_done = env_done;
-  a.valid = valid;
-  a.advantage = advantage;
-  a.value_target = value_target;
-  a.T = T;
-  a.E = E;
-  a.N = N;
-  a.gamma = gamma;
-  a.lam = lam;
-  const long long en = (long long)E * N;
-  // the per-CU cap (32 blocks of 256 threads) is mirrored by tests/test_gpu_value_rollout.py
-  hipLaunchKernelGGL(gae_agent_kernel, dim3(grid_for((en + 255) / 256, 32)), dim3(256), 0, (hipStream_t)hip_stream, a);
-  return launch_status();
+  return gae_launch<true>(reward, value, terminated, truncated, env_done, valid, T, E, N, gamma, lam, advantage,
+                          value_target, hip_stream, g_err);
 }
 
 }  // extern "C"

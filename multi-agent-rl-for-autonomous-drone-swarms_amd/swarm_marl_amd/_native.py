@@ -329,17 +329,20 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
     return lib
 
 
-def check(rc: int, lib: ctypes.CDLL | None = None, policy: bool = False, which: str | None = None) -> None:
+# the component whose last-error string explains a return code (`check`'s `which`)
+LAST_ERROR = {"policy": "swarm_policy_last_error", "attn": "swarm_attn_policy_last_error",
+              "eval": "swarm_eval_last_error", "critic": "swarm_critic_last_error", "ppo": "swarm_ppo_last_error",
+              "value": "swarm_value_last_error"}
+
+
+def check(rc: int, lib: ctypes.CDLL | None = None, which: str | None = None) -> None:
     """Raise on a negative return code (bad arguments -> ValueError, HIP errors -> RuntimeError).
-    `which` names the component whose last-error string explains it ("policy", "attn", "eval", "critic",
-    "ppo", "value")."""
+    `which` names the component whose last-error string explains it (a key of LAST_ERROR; the env's
+    swarm_last_error otherwise)."""
     if rc == SWARM_OK:
         return
     lib = lib or load_library()
-    which = "policy" if policy else which
-    err = (lib.swarm_critic_last_error if which == "critic" else lib.swarm_ppo_last_error if which == "ppo" else
-           lib.swarm_attn_policy_last_error if which == "attn" else lib.swarm_value_last_error if which == "value" else
-           {"policy": lib.swarm_policy_last_error, "eval": lib.swarm_eval_last_error}.get(which, lib.swarm_last_error))
+    err = getattr(lib, LAST_ERROR.get(which, "swarm_last_error"))  # looked up now: a library given by path may lack a unit
     msg = (err() or b"").decode(errors="replace")
     if rc in (SWARM_EINVAL, SWARM_ENULL, SWARM_ELIMIT):
         raise ValueError(f"swarm_mi355x error {rc}: {msg}")

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._mlp import _PRECISION, _Actor, _np
 
-_PRECISION = {"bf16": nat.POLICY_BF16, "f32": nat.POLICY_F32}
 EMBED = nat.ATTN_EMBED
 
 # the reference's parameter names -> shapes (the attention front end)
@@ -40,12 +40,6 @@ PARAM_SHAPES = {
 TRUNK_KEYS = tuple(f"action_model.{layer}._model.0.{part}"
                    for layer in ("_hidden_layers.0", "_hidden_layers.1", "_logits") for part in ("weight", "bias"))
 STATE_DICT_KEYS = tuple(PARAM_SHAPES) + TRUNK_KEYS
-
-
-def _np(a) -> np.ndarray:
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, np.float32)
 
 
 def unpack_bf16_blob(blob: np.ndarray, out_dim: int) -> dict:
@@ -64,9 +58,10 @@ def unpack_bf16_blob(blob: np.ndarray, out_dim: int) -> dict:
                 neighbor_b=fe[448:480], A=fe[480:1504].reshape(32, 32), c0=fe[1504:1536], w1=w1)
 
 
-class AttentionPolicy:
+class AttentionPolicy(_Actor):
     """`params`: the reference's eight front-end arrays by name (`PARAM_SHAPES`); `trunk_layers`: three
     (w, b) of the shapes [256, 41 + 4 Ms], [256, 256], [out, 256]."""
+    _forward, _which = "swarm_attn_policy_forward", "attn"
 
     def __init__(self, params, trunk_layers, *, neighbor_k: int, sensed_obstacles: int, device="cuda",
                  precision: str = "bf16"):
@@ -144,44 +139,6 @@ class AttentionPolicy:
         self.params, self.layers = self._validated(params, trunk_layers)
         self._pack()
         self.weights.copy_(torch.from_numpy(self.packed_host))
-
-    # ------------------------------------------------------------------ forward
-    def _check_obs(self, obs: torch.Tensor) -> int:
-        if not isinstance(obs, torch.Tensor) or obs.device != self.device or obs.dtype != torch.float32:
-            raise ValueError(f"obs must be a float32 tensor on {self.device}")
-        if obs.shape[-1] != self.in_dim or not obs.is_contiguous():
-            raise ValueError(f"obs must be contiguous [..., {self.in_dim}], got {tuple(obs.shape)}")
-        return int(obs.numel() // self.in_dim)
-
-    def forward(self, obs: torch.Tensor, *, logits: torch.Tensor | None = None,
-                actions: torch.Tensor | None = None, sample: bool = False, seed: int = 0,
-                counter: int = 0) -> None:
-        rows = self._check_obs(obs)
-        for name, t, width in (("logits", logits, self.out_dim), ("actions", actions, self.out_dim // 2)):
-            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()
-                                  or t.numel() != rows * width):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of {rows} x {width} on {self.device}")
-        mode = nat.POLICY_ACT_SAMPLE if sample else nat.POLICY_ACT_MEAN
-        rc = self.lib.swarm_attn_policy_forward(ctypes.byref(self._c), obs.data_ptr(), rows,
-                                                None if logits is None else logits.data_ptr(),
-                                                None if actions is None else actions.data_ptr(), mode,
-                                                int(seed) & (2**64 - 1), int(counter) & (2**64 - 1),
-                                                torch.cuda.current_stream(self.device).cuda_stream)
-        nat.check(rc, self.lib, which="attn")
-
-    def logits(self, obs: torch.Tensor) -> torch.Tensor:
-        out = torch.empty(obs.shape[:-1] + (self.out_dim,), dtype=torch.float32, device=self.device)
-        self.forward(obs, logits=out)
-        return out
-
-    def act(self, obs: torch.Tensor, out: torch.Tensor | None = None, *, deterministic: bool = True,
-            seed: int = 0, counter: int = 0) -> torch.Tensor:
-        """Actions [..., out/2]: the Gaussian mean, or mean + exp(log_std) * N(0, 1) (Philox keyed by
-        (seed, row, counter), `PolicyMLP`'s normals) with deterministic=False."""
-        if out is None:
-            out = torch.empty(obs.shape[:-1] + (self.out_dim // 2,), dtype=torch.float32, device=self.device)
-        self.forward(obs, actions=out, sample=not deterministic, seed=seed, counter=counter)
-        return out
 
 
 class _AttentionBlock(torch.nn.Module):

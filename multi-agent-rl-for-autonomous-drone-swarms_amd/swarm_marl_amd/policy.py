@@ -24,16 +24,15 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from ._mlp import _Actor, _fp
 from .onnx_weights import mlp_layers, read_onnx
 
 _PRECISION = {"bf16": nat.POLICY_BF16, "f32": nat.POLICY_F32, "f32x3": nat.POLICY_F32X3}
 
 
-def _fp(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+class PolicyMLP(_Actor):
+    _forward, _which = "swarm_policy_forward", "policy"
 
-
-class PolicyMLP:
     def __init__(self, layers, *, device="cuda", precision: str = "bf16"):
         if precision not in _PRECISION:
             raise ValueError(f"precision must be one of {sorted(_PRECISION)}, got {precision!r}")
@@ -52,11 +51,11 @@ class PolicyMLP:
         prec = _PRECISION[precision]
         nb = int(self.lib.swarm_policy_packed_bytes(self.in_dim, self.out_dim, prec))
         if nb < 0:
-            nat.check(nb, self.lib, policy=True)
+            nat.check(nb, self.lib, which="policy")
         host = np.zeros(nb, np.uint8)
         arrs = [np.ascontiguousarray(a, np.float32) for a in (w1, b1, w2, b2, w3, b3)]
         nat.check(self.lib.swarm_policy_pack(self.in_dim, self.out_dim, prec, *map(_fp, arrs),
-                                             host.ctypes.data_as(ctypes.c_void_p)), self.lib, policy=True)
+                                             host.ctypes.data_as(ctypes.c_void_p)), self.lib, which="policy")
         self.packed_host = host
         self.weights = torch.from_numpy(host).to(self.device)  # caching allocator: 256-B aligned
         self._c = nat.SwarmPolicy(self.in_dim, self.out_dim, prec, 0, self.weights.data_ptr())
@@ -80,46 +79,6 @@ class PolicyMLP:
                                    zip(arrs, (x for wb in self.layers for x in (wb[0], np.reshape(wb[1], -1))))):
             raise ValueError(f"expected 3 layers of the shapes {[w.shape for w, _ in self.layers]}")
         nat.check(self.lib.swarm_policy_pack(self.in_dim, self.out_dim, _PRECISION[self.precision], *map(_fp, arrs),
-                                             self.packed_host.ctypes.data_as(ctypes.c_void_p)), self.lib, policy=True)
+                                             self.packed_host.ctypes.data_as(ctypes.c_void_p)), self.lib, which="policy")
         self.weights.copy_(torch.from_numpy(self.packed_host))
         self.layers = [(arrs[2 * i].copy(), arrs[2 * i + 1].copy()) for i in range(3)]
-
-    # ------------------------------------------------------------------ forward
-    def _check_obs(self, obs: torch.Tensor) -> int:
-        if not isinstance(obs, torch.Tensor) or obs.device != self.device or obs.dtype != torch.float32:
-            raise ValueError(f"obs must be a float32 tensor on {self.device}")
-        if obs.shape[-1] != self.in_dim or not obs.is_contiguous():
-            raise ValueError(f"obs must be contiguous [..., {self.in_dim}], got {tuple(obs.shape)}")
-        return int(obs.numel() // self.in_dim)
-
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def forward(self, obs: torch.Tensor, *, logits: torch.Tensor | None = None,
-                actions: torch.Tensor | None = None, sample: bool = False, seed: int = 0,
-                counter: int = 0) -> None:
-        rows = self._check_obs(obs)
-        for name, t, width in (("logits", logits, self.out_dim), ("actions", actions, self.out_dim // 2)):
-            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()
-                                  or t.numel() != rows * width):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of {rows} x {width} on {self.device}")
-        mode = nat.POLICY_ACT_SAMPLE if sample else nat.POLICY_ACT_MEAN
-        rc = self.lib.swarm_policy_forward(ctypes.byref(self._c), obs.data_ptr(), rows,
-                                           None if logits is None else logits.data_ptr(),
-                                           None if actions is None else actions.data_ptr(), mode,
-                                           int(seed) & (2**64 - 1), int(counter) & (2**64 - 1), self._stream())
-        nat.check(rc, self.lib, policy=True)
-
-    def logits(self, obs: torch.Tensor) -> torch.Tensor:
-        out = torch.empty(obs.shape[:-1] + (self.out_dim,), dtype=torch.float32, device=self.device)
-        self.forward(obs, logits=out)
-        return out
-
-    def act(self, obs: torch.Tensor, out: torch.Tensor | None = None, *, deterministic: bool = True,
-            seed: int = 0, counter: int = 0) -> torch.Tensor:
-        """Actions [..., out/2]: the Gaussian mean, or mean + exp(log_std) * N(0, 1) (Philox keyed by
-        (seed, row, counter)) with deterministic=False."""
-        if out is None:
-            out = torch.empty(obs.shape[:-1] + (self.out_dim // 2,), dtype=torch.float32, device=self.device)
-        self.forward(obs, actions=out, sample=not deterministic, seed=seed, counter=counter)
-        return out

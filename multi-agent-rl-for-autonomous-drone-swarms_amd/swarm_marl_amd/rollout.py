@@ -29,15 +29,12 @@ from __future__ import annotations
 import torch
 
 from . import _native as nat
+from ._mlp import _stream
 from .attention import AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
 from .value import AgentValueMLP
 from .vec_env import VecSwarm
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _check(name: str, t, shape, dtypes, device=None) -> None:
@@ -75,16 +72,18 @@ def gaussian_logp(logits: torch.Tensor, actions: torch.Tensor, out: torch.Tensor
 
 def gae(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor,
         env_done: torch.Tensor, valid: torch.Tensor, *, gamma: float = 0.99, lam: float = 0.95,
-        advantage: torch.Tensor | None = None, value_target: torch.Tensor | None = None):
+        advantage: torch.Tensor | None = None, value_target: torch.Tensor | None = None, per_agent: bool = False):
     """(advantage, value_target) [T, E, N] of a fragment (swarm_gae; the loop in
     include/swarm_mi355x.h, bit for bit an f32 NumPy loop).  reward / terminated / truncated /
-    valid [T, E, N], value [T+1, E], env_done [T, E] SWARM_ENV_* bits; flags uint8 or bool."""
+    valid [T, E, N], value [T+1, E], env_done [T, E] SWARM_ENV_* bits; flags uint8 or bool.
+    per_agent=True: a per-agent value [T+1, E, N] (swarm_gae_agent).  value[t] of an invalid step and
+    value[t+1] behind an invalid or done step are never read."""
     if not isinstance(reward, torch.Tensor) or reward.dim() != 3:
         raise ValueError("reward must be a tensor [T, E, N]")
     t, e, n = (int(s) for s in reward.shape)
     dev = reward.device
     _check("reward", reward, (t, e, n), _F32)
-    _check("value", value, (t + 1, e), _F32, dev)
+    _check("value", value, (t + 1, e, n) if per_agent else (t + 1, e), _F32, dev)
     for name, x in (("terminated", terminated), ("truncated", truncated), ("valid", valid)):
         _check(name, x, (t, e, n), _U8, dev)
     _check("env_done", env_done, (t, e), _U8, dev)
@@ -95,38 +94,16 @@ def gae(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, tru
     _check("advantage", advantage, (t, e, n), _F32, dev)
     _check("value_target", value_target, (t, e, n), _F32, dev)
     lib = nat.load_library()
-    nat.check(lib.swarm_gae(reward.data_ptr(), value.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
-                            env_done.data_ptr(), valid.data_ptr(), t, e, n, float(gamma), float(lam),
-                            advantage.data_ptr(), value_target.data_ptr(), _stream(dev)), lib, which="critic")
+    fn, which = (lib.swarm_gae_agent, "value") if per_agent else (lib.swarm_gae, "critic")
+    nat.check(fn(reward.data_ptr(), value.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                 env_done.data_ptr(), valid.data_ptr(), t, e, n, float(gamma), float(lam),
+                 advantage.data_ptr(), value_target.data_ptr(), _stream(dev)), lib, which=which)
     return advantage, value_target
 
 
-def gae_agent(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor,
-              env_done: torch.Tensor, valid: torch.Tensor, *, gamma: float = 0.99, lam: float = 0.95,
-              advantage: torch.Tensor | None = None, value_target: torch.Tensor | None = None):
-    """`gae` with a per-agent value [T+1, E, N] (swarm_gae_agent; the loop in include/swarm_mi355x.h,
-    bit for bit an f32 NumPy loop).  value[t, e, n] of an invalid step and value[t+1, e, n] behind an
-    invalid or done step are never read."""
-    if not isinstance(reward, torch.Tensor) or reward.dim() != 3:
-        raise ValueError("reward must be a tensor [T, E, N]")
-    t, e, n = (int(s) for s in reward.shape)
-    dev = reward.device
-    _check("reward", reward, (t, e, n), _F32)
-    _check("value", value, (t + 1, e, n), _F32, dev)
-    for name, x in (("terminated", terminated), ("truncated", truncated), ("valid", valid)):
-        _check(name, x, (t, e, n), _U8, dev)
-    _check("env_done", env_done, (t, e), _U8, dev)
-    if advantage is None:
-        advantage = torch.empty((t, e, n), dtype=torch.float32, device=dev)
-    if value_target is None:
-        value_target = torch.empty((t, e, n), dtype=torch.float32, device=dev)
-    _check("advantage", advantage, (t, e, n), _F32, dev)
-    _check("value_target", value_target, (t, e, n), _F32, dev)
-    lib = nat.load_library()
-    nat.check(lib.swarm_gae_agent(reward.data_ptr(), value.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
-                                  env_done.data_ptr(), valid.data_ptr(), t, e, n, float(gamma), float(lam),
-                                  advantage.data_ptr(), value_target.data_ptr(), _stream(dev)), lib, which="value")
-    return advantage, value_target
+def gae_agent(*args, **kw):
+    """`gae` with a per-agent value [T+1, E, N]: gae(..., per_agent=True)."""
+    return gae(*args, per_agent=True, **kw)
 
 
 class RolloutCollector:
@@ -216,10 +193,6 @@ class RolloutCollector:
         elif self.critic is not None:
             self.critic.value(self.global_state, out=self.value)
         gaussian_logp(self.logits, self.actions, out=self.logp)
-        if self.per_agent:
-            gae_agent(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid,
-                      gamma=self.gamma, lam=self.lam, advantage=self.advantage, value_target=self.value_target)
-            return self._batch
-        gae(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid,
-            gamma=self.gamma, lam=self.lam, advantage=self.advantage, value_target=self.value_target)
+        gae(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid, gamma=self.gamma,
+            lam=self.lam, advantage=self.advantage, value_target=self.value_target, per_agent=self.per_agent)
         return self._batch

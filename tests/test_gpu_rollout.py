@@ -71,7 +71,7 @@ def test_gaussian_logp_other_action_dims(dev, adim, rows):
 
 def _one_pass_threads(dev) -> int:
     """Threads of one pass of the log-prob / GAE grid: 32 blocks of 256 per CU (the cap of their
-    grid_for calls in csrc/swarm_critic.hip, mirrored here)."""
+    grid_for calls in csrc/swarm_critic.hip and gae_launch, csrc/swarm_nn.h, mirrored here)."""
     return torch.cuda.get_device_properties(dev).multi_processor_count * 32 * 256
 
 

@@ -71,7 +71,7 @@ def test_gae_agent_bitwise_vs_numpy_f32(dev, shape, gamma, lam):
 
 def _one_pass_threads(dev) -> int:
     """Threads of one pass of the GAE grid: 32 blocks of 256 per CU (the cap of swarm_gae_agent's
-    grid_for call in csrc/swarm_value.hip, mirrored here)."""
+    grid_for call, gae_launch in csrc/swarm_nn.h, mirrored here)."""
     return torch.cuda.get_device_properties(dev).multi_processor_count * 32 * 256
 
 
