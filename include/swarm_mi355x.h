@@ -295,7 +295,8 @@ int swarm_observe(const swarm_params_t* p, const swarm_state_t* s, const uint8_t
                                        speed); obs, weights and activations must be < 65504 in
                                        magnitude (f16 range) */
 #define SWARM_POLICY_ACT_MEAN 0     /* actions = mean (deterministic) */
-#define SWARM_POLICY_ACT_SAMPLE 1   /* actions = mean + exp(log_std) * N(0,1), Philox(seed; row, counter) */
+#define SWARM_POLICY_ACT_SAMPLE 1   /* actions = mean + exp(log_std) * N(0,1), Philox(seed; row, counter); every
+                                       precision, the same normals in each */
 
 typedef struct swarm_policy {
   int32_t in_dim;        /* observation width D */
@@ -314,7 +315,10 @@ int swarm_policy_pack(int in_dim, int out_dim, int precision, const float* w1, c
                       const float* b2, const float* w3, const float* b3, void* host_out);
 
 /* logits [rows,out] (nullable) and/or actions [rows,out/2] (nullable) for obs [rows,in]; async on
- * hip_stream, no allocation, no sync. */
+ * hip_stream, no allocation, no sync.  SWARM_POLICY_ACT_SAMPLE works in every precision: row r
+ * draws its normals from Philox(seed; r, counter) whatever the precision (and in
+ * swarm_attn_policy_forward), and a = mean + expf(log_std) * z is formed in the same f32 order, so
+ * equal logits give equal actions bit for bit.  The logits written are those of a mean-mode launch. */
 int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long rows, float* logits, float* actions,
                          int action_mode, unsigned long long seed, unsigned long long counter, void* hip_stream);
 

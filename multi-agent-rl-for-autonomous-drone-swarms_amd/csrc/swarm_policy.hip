@@ -306,7 +306,11 @@ __device__ __forceinline__ float wload(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
   return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)(sbase + soff_floats * 4u), 0));
 }
 
-template <int WAVES>
+// The sampling instance takes 135 VGPRs + 64 AGPRs (two waves per SIMD; the mean instance 99 + 64,
+// three) and runs 1.20 x the mean instance's time.  Asked for three waves
+// (amdgpu_waves_per_eu(MODE == SWARM_POLICY_ACT_SAMPLE ? 3 : 1)) it fits 160 VGPRs and no AGPRs
+// without scratch, and measured 2.26 x.
+template <int WAVES, int MODE>
 __global__ void __launch_bounds__(64 * WAVES) policy_mlp_f32(const FwdArgs A) {
   const F32Layout L(A.in);
   const __amdgpu_buffer_rsrc_t W =
@@ -372,11 +376,37 @@ __global__ void __launch_bounds__(64 * WAVES) policy_mlp_f32(const FwdArgs A) {
       for (int i = 0; i < 4; ++i)
         if (4 * g + i < out) A.logits[row * out + 4 * g + i] = acc[i];
     }
-    if (A.actions && valid) {
-      const int ad = out / 2;
+    if constexpr (MODE == SWARM_POLICY_ACT_MEAN) {
+      if (A.actions && valid) {
+        const int ad = out / 2;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (4 * g + i < ad) A.actions[row * ad + 4 * g + i] = acc[i];
+        for (int i = 0; i < 4; ++i)
+          if (4 * g + i < ad) A.actions[row * ad + 4 * g + i] = acc[i];
+      }
+    } else if (A.actions) {
+      // gather the row's logits 0..11 on the writing lane (quarter g = 0) from lanes n + 16 and
+      // n + 32 (out <= 12: quarter 3 holds none); every lane runs the shuffles, only the draw and
+      // the store are predicated
+      float lg[12];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        lg[i] = acc[i];
+        lg[4 + i] = __shfl(acc[i], n + 16);
+        lg[8 + i] = __shfl(acc[i], n + 32);
+      }
+      const int ad = out / 2;
+      if (g == 0 && valid) {
+        float z[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        SWARM_NORMALS(A, row, ad, z)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          if (k < ad) {
+            float a = lg[k];
+            a = a + expf(lg[ad + k]) * z[k];  // policy_mlp_bf16's expression and order
+            A.actions[row * ad + k] = a;
+          }
+        }
+      }
     }
   }
 }
@@ -443,7 +473,7 @@ __device__ __forceinline__ f32x16 x3_sum(const f32x16& c, const f32x16& x) {
   return r;
 }
 
-template <int WAVES, int IN_C = 0, int OUT_C = 0>
+template <int WAVES, int MODE, int IN_C = 0, int OUT_C = 0>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4 > 0 ? WAVES / 4 : 1)))
 policy_mlp_x3(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -664,9 +694,17 @@ policy_mlp_x3(const FwdArgs A) {
       }
       const int ad = out / 2;
       if (h == 0 && valid) {
+        if constexpr (MODE == SWARM_POLICY_ACT_SAMPLE) {  // policy_mlp_bf16's epilogue
+          float z[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          SWARM_NORMALS(A, row, ad, z)
 #pragma unroll
-        for (int k = 0; k < 6; ++k)
-          if (k < ad) A.actions[row * ad + k] = lg[k];
+          for (int k = 0; k < 6; ++k)
+            if (k < ad) A.actions[row * ad + k] = lg[k] + expf(lg[ad + k]) * z[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            if (k < ad) A.actions[row * ad + k] = lg[k];
+        }
       }
     }
   }
@@ -688,7 +726,7 @@ policy_mlp_x3(const FwdArgs A) {
 #ifndef X3L_AHEAD
 #define X3L_AHEAD 1  // W2 lo fragments in flight ahead of their MFMAs (divides 16; 2 / 4 / 8 no faster, r06u)
 #endif
-template <int WAVES>
+template <int WAVES, int MODE>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4 > 0 ? WAVES / 4 : 1)))
 policy_mlp_x3l(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -845,9 +883,17 @@ policy_mlp_x3l(const FwdArgs A) {
       }
       const int ad = out / 2;
       if (h == 0 && valid) {
+        if constexpr (MODE == SWARM_POLICY_ACT_SAMPLE) {  // policy_mlp_bf16's epilogue
+          float z[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          SWARM_NORMALS(A, row, ad, z)
 #pragma unroll
-        for (int k = 0; k < 6; ++k)
-          if (k < ad) A.actions[row * ad + k] = lg[k];
+          for (int k = 0; k < 6; ++k)
+            if (k < ad) A.actions[row * ad + k] = lg[k] + expf(lg[ad + k]) * z[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 6; ++k)
+            if (k < ad) A.actions[row * ad + k] = lg[k];
+        }
       }
     }
   }
@@ -985,8 +1031,6 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
   if (!logits && !actions) return g_err.fail(SWARM_ENULL, "need logits and/or actions");
   if (action_mode != SWARM_POLICY_ACT_MEAN && action_mode != SWARM_POLICY_ACT_SAMPLE)
     return g_err.fail(SWARM_EINVAL, "unknown action_mode");
-  if (action_mode == SWARM_POLICY_ACT_SAMPLE && p->precision != SWARM_POLICY_BF16)
-    return g_err.fail(SWARM_EINVAL, "sampled actions are implemented on the bf16 path");
   if (((uintptr_t)p->weights) % 16) return g_err.fail(SWARM_EINVAL, "weights must be 16-B aligned");
   FwdArgs a;
   a.w = p->weights;
@@ -1021,7 +1065,9 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
     (void)dflt;  // the compile-time-dims instance spills (71 VGPRs at 512); the runtime-dims one fits (492)
     const char* pipe = getenv("SWARM_POLICY_X3_PIPELINED");
     const bool lean = !(pipe && pipe[0] == '1');
-    auto fn = lean ? policy_mlp_x3l<X3L_WAVES> : policy_mlp_x3<X3_WAVES>;
+    const bool smp = action_mode == SWARM_POLICY_ACT_SAMPLE;
+    auto fn = lean ? (smp ? policy_mlp_x3l<X3L_WAVES, SWARM_POLICY_ACT_SAMPLE> : policy_mlp_x3l<X3L_WAVES, SWARM_POLICY_ACT_MEAN>)
+                   : (smp ? policy_mlp_x3<X3_WAVES, SWARM_POLICY_ACT_SAMPLE> : policy_mlp_x3<X3_WAVES, SWARM_POLICY_ACT_MEAN>);
     const int waves = lean ? X3L_WAVES : X3_WAVES;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
         hipSuccess)
@@ -1030,7 +1076,9 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * waves), lds, s, a);
   } else {
     const int grid = tile_grid(F32_WAVES, (rows + 15) / 16) * 2;
-    hipLaunchKernelGGL(policy_mlp_f32<F32_WAVES>, dim3(grid), dim3(64 * F32_WAVES), 0, s, a);
+    auto fn = action_mode == SWARM_POLICY_ACT_SAMPLE ? policy_mlp_f32<F32_WAVES, SWARM_POLICY_ACT_SAMPLE>
+                                                     : policy_mlp_f32<F32_WAVES, SWARM_POLICY_ACT_MEAN>;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * F32_WAVES), 0, s, a);
   }
   return g_err.launch_status();
 }
