@@ -293,7 +293,10 @@ int swarm_observe(const swarm_params_t* p, const swarm_state_t* s, const uint8_t
                                        into f16 hi + lo, products hi*hi + hi*lo + lo*hi (~2^-21
                                        relative per product: the f32 path's tolerance at f16-MFMA
                                        speed); obs, weights and activations must be < 65504 in
-                                       magnitude (f16 range) */
+                                       magnitude (f16 range).  swarm_policy_pack returns SWARM_EINVAL
+                                       and leaves host_out untouched when a W1, b1, W2 or W3 entry is
+                                       not finite or rounds past 65504 in f16 (|v| >= 65520); b2 and
+                                       b3 stay f32 and are not checked */
 #define SWARM_POLICY_ACT_MEAN 0     /* actions = mean (deterministic) */
 #define SWARM_POLICY_ACT_SAMPLE 1   /* actions = mean + exp(log_std) * N(0,1), Philox(seed; row, counter); every
                                        precision, the same normals in each */

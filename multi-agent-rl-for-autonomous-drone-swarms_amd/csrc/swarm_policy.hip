@@ -938,6 +938,17 @@ int swarm_policy_pack(int in_dim, int out_dim, int precision, const float* w1, c
   const long long nb = swarm_policy_packed_bytes(in_dim, out_dim, precision);
   if (nb < 0) return (int)nb;
   if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !host_out) return g_err.fail(SWARM_ENULL, "null weight pointer");
+  if (precision == SWARM_POLICY_F32X3) {
+    // the f16 domain of the split operands: one inf or NaN hi piece reaches every row of every launch
+    // (b2 and b3 stay f32).  Checked before host_out is touched: a refused repack keeps the old blob.
+    auto in_f16 = [](const float* v, size_t n) {
+      for (size_t i = 0; i < n; ++i)
+        if ((f16_rne(v[i]) & 0x7c00u) == 0x7c00u) return false;  // inf or NaN: |v| >= 65520 or not finite
+      return true;
+    };
+    if (!in_f16(w1, (size_t)H * in_dim) || !in_f16(b1, H) || !in_f16(w2, (size_t)H * H) || !in_f16(w3, (size_t)out_dim * H))
+      return g_err.fail(SWARM_EINVAL, "f32x3 weights outside the f16 range (W1, b1, W2, W3 must be finite and round to at most 65504)");
+  }
   memset(host_out, 0, (size_t)nb);
   if (precision == SWARM_POLICY_F32X3) {
     // the bf16 blob's fragment order twice, f16 elements: hi = f16(v), then lo = f16((v - hi) 2^11)

@@ -14,7 +14,9 @@ launches (policy, env step) with no host round trip:
 precision "bf16" (default): bf16 MFMA operands with f32 accumulation (~1e-2 relative on the
 logits); "f32": f32 MFMA (within summation-order rounding of the f32 graph); "f32x3": the f32
 graph's accuracy on f16 MFMA — every operand split into f16 hi + lo, three products per term
-(hi*hi + hi*lo + lo*hi, ~2^-21 relative each); obs / weights / activations within the f16 range.
+(hi*hi + hi*lo + lo*hi, ~2^-21 relative each); obs / weights / activations within the f16 range
+(a W1, b1, W2 or W3 entry that is not finite or rounds past 65504 is refused with ValueError, by the
+constructor and by load_layers, which then keeps the old weights).
 """
 from __future__ import annotations
 

@@ -383,3 +383,83 @@ def test_emulations_are_generic_in_dims(shape):
     emu = emulate_bf16_kernel(_pack(lib, layers, nat.POLICY_BF16), x, shape[1])
     assert emu.shape == ref.shape and np.abs(emu - ref).max() < 0.05 * max(1.0, np.abs(ref).max())
     assert np.abs(emu - ref).max() > 1e-6  # it is the rounded arithmetic, not the float64 forward again
+
+
+def _pack_rc(lib, layers, precision, buf):
+    (w1, b1, _), (w2, b2, _), (w3, b3, _) = layers
+    keep = [np.ascontiguousarray(a, np.float32) for a in (w1, b1, w2, b2, w3, b3)]
+    return lib.swarm_policy_pack(w1.shape[1], w3.shape[0], precision,
+                                 *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) for a in keep],
+                                 buf.ctypes.data_as(ctypes.c_void_p))
+
+
+# (layer, is bias, flat index): one entry of W1, b1, W2, W3 each, away from index 0
+_X3_CHECKED = ((0, False, 37 * 200 + 36), (0, True, 255), (1, False, 256 * 131 + 77), (2, False, 256 * 5 + 255))
+
+
+@pytest.mark.parametrize("bad", [65520.0, -65520.0, np.nan, np.inf, -np.inf, 1e30])
+@pytest.mark.parametrize("where", _X3_CHECKED, ids=["w1", "b1", "w2", "w3"])
+def test_pack_f32x3_rejects_weights_outside_the_f16_range(where, bad):
+    """hi = f16(v) is inf from |v| = 65520 on (the tie to 65536 rounds to even) and one inf or NaN hi
+    piece reaches every row of every launch: swarm_policy_pack refuses it with SWARM_EINVAL, names the
+    f16 range and leaves host_out alone.  The bf16 and f32 blobs take any weight, as before."""
+    from swarm_marl_amd import _native as nat
+    from tests import policy_ref as pr
+    lib = nat.load_library()
+    layer, is_bias, idx = where
+    layers = [tuple(a.copy() if isinstance(a, np.ndarray) else a for a in l) for l in pr.make_actor(37, 6)]
+    layers[layer][1 if is_bias else 0].reshape(-1)[idx] = bad
+    nb = lib.swarm_policy_packed_bytes(37, 6, nat.POLICY_F32X3)
+    buf = np.full(nb, 0xA5, np.uint8)
+    assert _pack_rc(lib, layers, nat.POLICY_F32X3, buf) == nat.SWARM_EINVAL
+    assert b"f16 range" in lib.swarm_policy_last_error()
+    assert np.all(buf == 0xA5)
+    for prec in (nat.POLICY_BF16, nat.POLICY_F32):
+        assert _pack_rc(lib, layers, prec, np.zeros(lib.swarm_policy_packed_bytes(37, 6, prec), np.uint8)) == 0
+
+
+def test_pack_f32x3_takes_the_largest_f16_and_any_b2_b3():
+    """65504 and what rounds to it (just under 65520) pack; b2 and b3 stay f32 and are not checked."""
+    from swarm_marl_amd import _native as nat
+    from tests import policy_ref as pr
+    lib = nat.load_library()
+    layers = [tuple(a.copy() if isinstance(a, np.ndarray) else a for a in l) for l in pr.make_actor(37, 6)]
+    for (layer, is_bias, idx), v in zip(_X3_CHECKED, (65504.0, -65504.0, np.nextafter(np.float32(65520), np.float32(0)), 65504.0)):
+        layers[layer][1 if is_bias else 0].reshape(-1)[idx] = v
+    layers[1][1][3] = 1e30
+    layers[2][1][1] = -70000.0
+    buf = _pack(lib, layers, nat.POLICY_F32X3)
+    half = len(buf) // 2
+    hi = buf[:half - 1024 - 128].view(np.float16)
+    assert np.all(np.isfinite(hi)) and np.abs(hi.astype(np.float32)).max() == 65504.0
+    assert buf[half - 1024 - 128:half - 128].view(np.float32)[3] == np.float32(1e30)
+    assert buf[half - 128:half].view(np.float32)[1] == -70000.0
+
+
+def test_load_layers_refuses_f32x3_weights_outside_the_f16_range_and_keeps_the_old_ones():
+    """PPOLearner repacks trained weights through PolicyMLP.load_layers on every update: a refused
+    repack raises ValueError and leaves the host blob and `layers` as they were (the device copy is
+    made from the host blob only after a successful pack)."""
+    from swarm_marl_amd import _native as nat
+    from swarm_marl_amd.policy import PolicyMLP
+    from tests import policy_ref as pr
+    good = pr.make_actor(37, 6)
+    pol = PolicyMLP.__new__(PolicyMLP)  # no device here: the host side of __init__
+    pol.lib = nat.load_library()
+    pol.in_dim, pol.out_dim, pol.precision = 37, 6, "f32x3"
+    pol.packed_host = _pack(pol.lib, good, nat.POLICY_F32X3)
+    pol.layers = [(w.copy(), b.copy()) for w, b, _ in good]
+
+    class _NoCopy:  # stands in for the device blob: a refused repack must not reach it
+        def copy_(self, _):
+            raise AssertionError("device blob written after a refused pack")
+    pol.weights = _NoCopy()
+    blob = pol.packed_host.copy()
+    for bad in (65520.0, np.nan, np.inf):
+        new = [(w.copy(), b.copy(), r) for w, b, r in pr.make_actor(37, 6)]
+        new[1][0][7, 9] = bad
+        with pytest.raises(ValueError, match="f16 range"):
+            pol.load_layers(new)
+        assert np.array_equal(pol.packed_host, blob)
+        for (w, b), (gw, gb, _) in zip(pol.layers, good):
+            assert np.array_equal(w, gw) and np.array_equal(b, gb)
