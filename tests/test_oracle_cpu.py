@@ -68,16 +68,44 @@ def test_c_oracle_matches_reference_fixture(name):
     _check_against_fixture(d, st, out)
 
 
-@pytest.mark.parametrize("n,e,physics,k,ms,m", [
+_MULTISTEP = [
     (4, 40, False, 3, 4, 8), (16, 24, False, 3, 4, 8), (64, 6, False, 3, 4, 8),
     (33, 5, False, 5, 6, 7), (1, 30, False, 3, 4, 8), (24, 8, False, 0, 0, 0),
     (4, 20, True, 3, 4, 8), (16, 6, True, 3, 4, 8),
-])
-def test_c_oracle_matches_numpy_oracle_multistep(n, e, physics, k, ms, m):
+]
+# physics off K = 3, Ms = 4 and off the default scalars: the slot widths, damping laws, substep
+# counts and one parameter point of tests/test_gpu_physics_shapes.py (the reference of that module
+# is pinned to nothing but its two implementations agreeing)
+_LOW_G = dict(world_size=33.3, max_accel=7.7, goal_radius=10.0 / 3.0, max_speed=3.3, obstacle_radius=0.77,
+              gravity=-3.7, gravity_comp=3.1, substep_dt=1.0 / 120.0, ground_contact_height=0.4,
+              drone_contact_radius=0.4)
+_MULTISTEP_PHYSICS = [
+    (24, 10, 0, 4, 8, dict(damping_law=1)), (24, 10, 1, 2, 8, dict(physics_substeps=5)),
+    (32, 8, 4, 4, 8, dict(damping_law=1, physics_substeps=0)), (40, 6, 5, 6, 8, dict(physics_substeps=0)),
+    (24, 10, 8, 8, 8, dict(damping_law=1, physics_substeps=5)), (100, 3, 12, 16, 20, dict(damping_law=1)),
+    (40, 6, 16, 0, 5, dict(world_size=10.0)), (24, 10, 3, 4, 0, dict(world_size=5.0, damping_law=1)),
+    (1, 30, 3, 4, 8, dict(damping_law=1)), (3, 20, 3, 4, 8, {}),
+    (16, 12, 3, 4, 8, dict(_LOW_G, damping_law=1)), (33, 6, 3, 4, 8, dict(_LOW_G, physics_substeps=48)),
+    (16, 12, 3, 4, 8, dict(max_speed=0.7, goal_radius=6.0)),
+    (16, 12, 3, 4, 8, dict(max_speed=0.7, goal_radius=6.0, damping_law=1)),
+]
+
+
+def _extra_id(extra):
+    if all(extra.get(k) == v for k, v in _LOW_G.items()):
+        extra = dict(low_g=1, **{k: v for k, v in extra.items() if k not in _LOW_G})
+    return "+".join(f"{k}={v:.4g}" for k, v in extra.items()) or "defaults"
+
+
+@pytest.mark.parametrize("n,e,physics,k,ms,m,extra", [
+    pytest.param(*row, {}, id="-".join(str(v) for v in row)) for row in _MULTISTEP] + [
+    pytest.param(n, e, True, k, ms, m, extra, id=f"physics-{n}-{e}-{k}-{ms}-{m}-{_extra_id(extra)}")
+    for n, e, k, ms, m, extra in _MULTISTEP_PHYSICS])
+def test_c_oracle_matches_numpy_oracle_multistep(n, e, physics, k, ms, m, extra):
     from oracle import c_oracle as co
     from oracle import swarm_oracle as so
     cfg = so.make_cfg(num_drones=n, neighbor_k=k, sensed_obstacles=ms, num_obstacles=m,
-                      max_steps=4)
+                      max_steps=4, **extra)
     st_n, _ = so.reset_device(cfg, so.empty_state(cfg, e), physics=physics, seed=5, env_offset=3)
     st_c, out_c = co.run(cfg, so.empty_state(cfg, e), "reset", physics=physics, seed=5,
                          env_offset=3)
@@ -97,6 +125,9 @@ def test_c_oracle_matches_numpy_oracle_multistep(n, e, physics, k, ms, m):
             assert np.array_equal(st_c[key], st_n[key]), f"{key} t={t}"
         assert np.array_equal(st_c["active"].astype(bool), st_n["active"].astype(bool))
         assert np.array_equal((out_c["env_done"] & 4) != 0, out_n["reset"])
+        assert np.array_equal(out_c["terminated"].astype(bool), out_n["terminated"]), f"terminated t={t}"
+        assert np.array_equal(out_c["truncated"].astype(bool), out_n["truncated"]), f"truncated t={t}"
+        assert np.array_equal(out_c["dist_goal"], out_n["dist_goal"]), f"dist_goal t={t}"
 
 
 # Random123 known-answer vectors for philox4x32_10 (kat_vectors in the Random123 distribution)
