@@ -524,6 +524,107 @@ int swarm_gae_agent(const float* reward, const float* value, const uint8_t* term
 const char* swarm_value_last_error(void);
 
 /*
+ * Actuation and sensing perturbations (csrc/swarm_perturb.hip): the control delay, thrust noise and
+ * sensing noise of the reference's configs/domain_randomization_v1.yaml, as a layer before and
+ * after the env step.  swarm_step itself is unchanged: swarm_actuate turns the policy's actions into
+ * the actions the step is given, swarm_sense turns the step's obs into the obs the policy sees.
+ * Both are one async launch on hip_stream, allocate nothing, do not synchronise and keep no host
+ * state; every argument is a device pointer or a constant.  num_envs == 0 is a no-op.  Errors via
+ * swarm_perturb_last_error, before any launch.
+ *
+ * Noise: Philox4x32-10 with key (seed lo, seed hi) on the counter words
+ *     (g, n | block << 16 | stream << 30, episode[e], step)
+ * g = (uint32)(env_offset + e) the global env index, n the agent slot, episode[e] and
+ * step = step_count[e] read from the env state (swarm_state_t) when the kernel runs; stream 0
+ * actuation, 1 sensing, 2 the delay draw.  A block x0..x3 gives four normals, pair (x0, x1) z0, z1
+ * and pair (x2, x3) z2, z3, in f32:
+ *     u1 = ((x >> 8) + 0.5) * 2^-24;  u2 = (x' >> 8) * 2^-24;  r = sqrtf(-2 logf(u1))
+ *     z = r cosf(2 pi u2),  z' = r sinf(2 pi u2)              (2 pi = 6.28318530717958647692f)
+ * So the noise depends on (seed, global env, agent, episode, step) only: not on the calls made
+ * before, on how the envs are split into groups, or on env_offset shards.
+ */
+#define SWARM_PERTURB_MAX_DELAY 7      /* control delay in steps */
+#define SWARM_PERTURB_MAX_AGENTS 256   /* N */
+#define SWARM_PERTURB_MAX_K 16         /* neighbour slots */
+#define SWARM_PERTURB_MAX_MS 5         /* sensed obstacles */
+
+/* The discrete delay distribution: `count` values with cum[i] = (float)(probs[0] + .. + probs[i])
+ * (the sum in double), cum[count - 1] == 1. */
+typedef struct swarm_delay_table {
+  int32_t count;                                  /* 1 .. SWARM_PERTURB_MAX_DELAY + 1 */
+  int32_t values[SWARM_PERTURB_MAX_DELAY + 1];    /* each in [0, ring_slots) */
+  float cum[SWARM_PERTURB_MAX_DELAY + 1];
+} swarm_delay_table_t;
+
+/*
+ * swarm_actuate, per env e and agent n, with s = step_count[e] (the episode step about to be taken):
+ *     d = delay_override[e] if delay_override and delay_override[e] >= 0, else values[i] for the
+ *         first i with u < cum[i], u = (x0 >> 8) * 2^-24 of the block (g, 2 << 30, episode[e], 0)
+ *         (one draw per env and episode; a single-entry table draws nothing); d = min(d, ring_slots - 1)
+ *     c = fminf(fmaxf(actions[e,n,:], -1), 1);   ring[s % ring_slots, e, n, :] = c
+ *     u = ring[(s - d) % ring_slots, e, n, :] if d <= s else 0   (nothing commanded yet this episode)
+ *     eff[e,n,k] = u_k + thrust_noise_std[e] * z_k, k = 0..2, z of block 0 of stream 0 at step s;
+ *                  u_k itself, bit for bit, where thrust_noise_std is NULL or 0 for the env
+ *     delay_out[e] = d                                        (if delay_out is not NULL)
+ * The noise goes in before the env's own clip to [-1, 1].  A new episode (step_count back at 0, a
+ * new episode number: an auto-reset or swarm_reset) draws a new delay and starts an empty line with
+ * no host action.  Call it once per step, before swarm_step, from the first step of an episode on.
+ * With actions == NULL (then ring and eff must be NULL too) only delay_out is written.
+ */
+typedef struct swarm_actuate_args {
+  const float* actions;           /* [E,N,3] the policy's actions */
+  float* ring;                    /* [ring_slots,E,N,3] the delay line, owned by the caller */
+  const int32_t* delay_override;  /* [E] fixed delay, -1: draw; NULL: draw everywhere */
+  const float* thrust_noise_std;  /* [E]; NULL: none */
+  const int32_t* step_count;      /* [E] swarm_state_t.step_count */
+  const uint32_t* episode;        /* [E] swarm_state_t.episode */
+  float* eff;                     /* [E,N,3] what swarm_step is given */
+  int32_t* delay_out;             /* [E] or NULL */
+  swarm_delay_table_t delays;
+  int32_t ring_slots;             /* R in [1, SWARM_PERTURB_MAX_DELAY + 1], > every table value */
+  int32_t num_envs, num_drones;   /* E >= 0, N in [1, SWARM_PERTURB_MAX_AGENTS] */
+  int32_t reserved;
+  uint64_t seed;
+  int64_t env_offset;             /* global index of env 0 */
+} swarm_actuate_args_t;
+
+int swarm_actuate(const swarm_actuate_args_t* args, void* hip_stream);
+
+/*
+ * swarm_sense: out [E,N,D] from obs [E,N,D], D = 9 + 4 K + 4 Ms, row layout
+ * [pos 3 | vel 3 | goal - pos 3 | K x (rel 3, dist) | Ms x (rel 3, dist)]; obs is not written and
+ * out is another buffer.  step = step_count[e] and episode[e] as they stand after the step or reset
+ * that produced obs; sp / sv / so the env's position / velocity / obstacle std; f32 without fused
+ * multiply-add:
+ *   own block     n_k = sp z_k (block 0);  pos'_k = pos_k + n_k;  (goal - pos)'_k = (goal - pos)_k - n_k
+ *                 vel'_k = vel_k + sv z_k (block 1)
+ *   neighbour j   rel'_k = rel_k + sp z_k (block 2 + j);  dist' = sqrtf((x' x' + y' y') + z' z')
+ *   obstacle j    dist' = fmaxf(dist + so z0, 0) (block 2 + K + j); the vector stays
+ * Copied bit for bit: rows with active[e,n] == 0, neighbour and obstacle slots whose four floats are
+ * all zero (the padding of K > N - 1 or Ms > M), and every group whose std is NULL or 0 for the env.
+ * The same state gives the same out.
+ */
+typedef struct swarm_sense_args {
+  const float* obs;                 /* [E,N,D] */
+  const uint8_t* active;            /* [E,N] swarm_state_t.active */
+  const float* position_noise_std;  /* [E]; NULL: none */
+  const float* velocity_noise_std;  /* [E]; NULL: none */
+  const float* obstacle_noise_std;  /* [E]; NULL: none */
+  const int32_t* step_count;        /* [E] */
+  const uint32_t* episode;          /* [E] */
+  float* out;                       /* [E,N,D] */
+  uint64_t seed;
+  int64_t env_offset;
+  int32_t num_envs, num_drones;     /* E >= 0, N in [1, SWARM_PERTURB_MAX_AGENTS] */
+  int32_t neighbor_k;               /* K in [0, SWARM_PERTURB_MAX_K] */
+  int32_t sensed_obstacles;         /* Ms in [0, SWARM_PERTURB_MAX_MS] */
+} swarm_sense_args_t;
+
+int swarm_sense(const swarm_sense_args_t* args, void* hip_stream);
+
+const char* swarm_perturb_last_error(void);
+
+/*
  * PPO loss head (csrc/swarm_ppo.hip): RLlib's PPOTorchPolicy.loss over a collected fragment, value
  * and gradient in one pass.  Rows are grouped by env-row: an env-row is one (t, e) with its N
  * consecutive agent rows (the collector's [T,E,N,...] flatten); values are per env-row.

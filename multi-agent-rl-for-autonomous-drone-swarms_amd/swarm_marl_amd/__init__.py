@@ -5,16 +5,19 @@ Host side of the C-ABI in include/swarm_mi355x.h.  `VecSwarm` is the batched ten
 (with `gaussian_logp` and `gae`) turn a device rollout into a PPO-ready batch; `PPOLearner` (with
 `ppo_loss` and `masked_moments`) trains on it.  `AttentionPolicy` is the reference's attention actor
 on the device, `AttentionActor` its trainable torch module.  `AgentValueMLP` (with `gae_agent`) is the
-per-agent critic of the reference's multi-agent and single-agent PPO set-ups.
+per-agent critic of the reference's multi-agent and single-agent PPO set-ups.  `Perturbation` (with
+`noise_spec`) is the control delay, thrust noise and sensing noise of the domain-randomisation recipe.
 """
 from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .envs.common import DroneEnvConfig
+from .perturbation import Perturbation, noise_spec
 from .ppo import PPOLearner, masked_moments, ppo_loss
 from .rollout import RolloutCollector, gae, gae_agent, gaussian_logp
 from .value import AgentValueMLP
 from .vec_env import VecSwarm
 
 __all__ = ["AgentValueMLP", "AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner",
-           "RolloutCollector", "VecSwarm", "gae", "gae_agent", "gaussian_logp", "masked_moments", "ppo_loss"]
+           "Perturbation", "RolloutCollector", "VecSwarm", "gae", "gae_agent", "gaussian_logp", "masked_moments",
+           "noise_spec", "ppo_loss"]
 __version__ = "0.1.0"

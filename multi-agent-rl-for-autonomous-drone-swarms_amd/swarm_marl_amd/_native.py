@@ -68,6 +68,10 @@ PPO_MAX_AGENTS = 256
 PPO_WORKSPACE_BYTES = 65536
 PPO_MOMENTS = 4
 PPO_STATS = 7
+PERTURB_MAX_DELAY = 7
+PERTURB_MAX_AGENTS = 256
+PERTURB_MAX_K = 16
+PERTURB_MAX_MS = 5
 
 # every symbol include/swarm_mi355x.h declares
 EXPORTED_SYMBOLS = (
@@ -79,6 +83,7 @@ EXPORTED_SYMBOLS = (
     "swarm_eval_begin", "swarm_eval_update", "swarm_eval_single_update", "swarm_eval_last_error",
     "swarm_env_cfg_set", "swarm_env_cfg_set_drones",
     "swarm_value_packed_bytes", "swarm_value_pack", "swarm_value_forward", "swarm_gae_agent", "swarm_value_last_error",
+    "swarm_actuate", "swarm_sense", "swarm_perturb_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
     "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
@@ -89,6 +94,7 @@ ROLLOUT_SYMBOLS = EXPORTED_SYMBOLS[-9:-3]
 PPO_SYMBOLS = EXPORTED_SYMBOLS[-3:]
 ATTN_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_attn_"))  # csrc/swarm_attn.hip
 VALUE_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_value_")) + ("swarm_gae_agent",)  # csrc/swarm_value.hip
+PERTURB_SYMBOLS = ("swarm_actuate", "swarm_sense", "swarm_perturb_last_error")  # csrc/swarm_perturb.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -190,6 +196,29 @@ class SwarmCritic(ctypes.Structure):
 class SwarmValue(ctypes.Structure):
     """swarm_value_t."""
     _fields_ = [("in_dim", ctypes.c_int32), ("precision", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
+class SwarmDelayTable(ctypes.Structure):
+    """swarm_delay_table_t."""
+    _fields_ = [("count", ctypes.c_int32), ("values", ctypes.c_int32 * (PERTURB_MAX_DELAY + 1)),
+                ("cum", ctypes.c_float * (PERTURB_MAX_DELAY + 1))]
+
+
+class SwarmActuateArgs(ctypes.Structure):
+    """swarm_actuate_args_t."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("actions", "ring", "delay_override", "thrust_noise_std", "step_count", "episode", "eff",
+                 "delay_out")] + [("delays", SwarmDelayTable)] + [
+        (name, ctypes.c_int32) for name in ("ring_slots", "num_envs", "num_drones", "reserved")] + [
+        ("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64)]
+
+
+class SwarmSenseArgs(ctypes.Structure):
+    """swarm_sense_args_t."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("obs", "active", "position_noise_std", "velocity_noise_std", "obstacle_noise_std", "step_count",
+                 "episode", "out")] + [("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64)] + [
+        (name, ctypes.c_int32) for name in ("num_envs", "num_drones", "neighbor_k", "sensed_obstacles")]
 
 
 class SwarmPpoArgs(ctypes.Structure):
@@ -314,6 +343,13 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
                                         ctypes.c_float, ctypes.c_float, vp, vp, vp]
         lib.swarm_value_last_error.restype = ctypes.c_char_p
         lib.swarm_value_last_error.argtypes = []
+    if path is None or all(hasattr(lib, name) for name in PERTURB_SYMBOLS):
+        lib.swarm_actuate.restype = ctypes.c_int
+        lib.swarm_actuate.argtypes = [ctypes.POINTER(SwarmActuateArgs), vp]
+        lib.swarm_sense.restype = ctypes.c_int
+        lib.swarm_sense.argtypes = [ctypes.POINTER(SwarmSenseArgs), vp]
+        lib.swarm_perturb_last_error.restype = ctypes.c_char_p
+        lib.swarm_perturb_last_error.argtypes = []
     if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
         lib.swarm_masked_moments.restype = ctypes.c_int
         lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -332,7 +368,7 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 # the component whose last-error string explains a return code (`check`'s `which`)
 LAST_ERROR = {"policy": "swarm_policy_last_error", "attn": "swarm_attn_policy_last_error",
               "eval": "swarm_eval_last_error", "critic": "swarm_critic_last_error", "ppo": "swarm_ppo_last_error",
-              "value": "swarm_value_last_error"}
+              "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error"}
 
 
 def check(rc: int, lib: ctypes.CDLL | None = None, which: str | None = None) -> None:

@@ -16,10 +16,11 @@ parameters, as per-env parameter records (swarm_env_cfg_t), entirely on the devi
 Each env's NEXT episode parameters are drawn ahead (torch RNG on the device) into
 `env_cfg_next`; the step kernel switches an env to them when it resets it, and `after_step()`
 draws fresh ones for exactly the envs the step reset (mask from env_done, no host sync).  The
-entries without a counterpart in the swarm env — mass_scale (the kinematic env has no mass; the
-physics restatement has no mass parameter), actuation delay / thrust noise and sensing noise
-(they would change the observation contract the parity tests pin) — are reported in
-`unsupported`, not silently dropped.
+entries that are not scale factors of an env parameter are reported in `unsupported`, not silently
+dropped: mass_scale has no counterpart (the kinematic env has no mass; the physics restatement has
+no mass parameter); the actuation delay, thrust noise and sensing noise are applied by
+`perturbation.Perturbation`, a layer before and after the step, not by this module.
+`RolloutCollector(randomizer=...)` calls `after_step()` inside a fragment.
 """
 from __future__ import annotations
 

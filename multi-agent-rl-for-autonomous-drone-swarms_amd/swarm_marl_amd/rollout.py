@@ -23,6 +23,13 @@ multi-agent and single-agent PPO set-ups) the value is per agent, V(obs[t, e, n]
 go into one [T+1, E, N, D] block (row T: the env's obs after the last step), one value launch runs
 over the whole block and `gae_agent` reads value[t, e, n].  The bootstrap rules are the same; no
 global_state is needed.
+
+With `perturb=` (a `Perturbation`) the policy acts on what it sensed and the env is
+given what the actuators did: obs[t] is `perturb.sense()` of the env's obs (row T of `obs_block`
+too, for the per-agent critic) and the step goes through `perturb.step`; actions and logp stay the
+policy's own, and global_state stays true (the centralized critic is privileged).  With
+`randomizer=` (a `DomainRandomizer`) its `after_step()` runs after every step of the fragment, so
+envs that reset inside one get fresh next-episode draws.  Both stay on the device.
 """
 from __future__ import annotations
 
@@ -121,7 +128,7 @@ class RolloutCollector:
 
     def __init__(self, vec: VecSwarm, policy: PolicyMLP | AttentionPolicy, critic: CriticMLP | AgentValueMLP | None = None, *,
                  horizon: int,
-                 gamma: float = 0.99, lam: float = 0.95, seed: int = 0):
+                 gamma: float = 0.99, lam: float = 0.95, seed: int = 0, perturb=None, randomizer=None):
         t = int(horizon)
         if t < 1:
             raise ValueError(f"horizon must be >= 1, got {horizon}")
@@ -143,7 +150,11 @@ class RolloutCollector:
             if critic.in_dim != g or critic.device != vec.device:
                 raise ValueError(f"critic takes {critic.in_dim} inputs on {critic.device}, the env's global_state "
                                  f"is {g} wide on {vec.device}")
+        for name, hook in (("perturb", perturb), ("randomizer", randomizer)):
+            if hook is not None and hook.vec is not vec:
+                raise ValueError(f"{name} belongs to another VecSwarm than the collector's")
         self.vec, self.policy, self.critic = vec, policy, critic
+        self.perturb, self.randomizer = perturb, randomizer
         self.horizon, self.gamma, self.lam, self.seed = t, float(gamma), float(lam), int(seed)
         self.counter = 0  # policy steps taken: the Philox counter of the next one
         kw = dict(device=vec.device)
@@ -171,24 +182,33 @@ class RolloutCollector:
         """One fragment from the env's current state (reset the env before the first call).
         deterministic=True acts with the Gaussian mean (evaluation): logp is then the log-density
         at the mean."""
-        vec, pol = self.vec, self.policy
+        vec, pol, per, rnd = self.vec, self.policy, self.perturb, self.randomizer
+        step = vec.step if per is None else per.step
         for t in range(self.horizon):
             self.valid[t].copy_(vec.active)
-            self.obs[t].copy_(vec.obs)
+            if per is None:
+                self.obs[t].copy_(vec.obs)
+            else:
+                per.sense(out=self.obs[t])
             if self.global_state is not None:
                 self.global_state[t].copy_(vec.global_state)
             pol.forward(self.obs[t], logits=self.logits[t], actions=self.actions[t], sample=not deterministic,
                         seed=self.seed, counter=self.counter)
             self.counter += 1
-            _, reward, terminated, truncated, env_done = vec.step(self.actions[t])
+            _, reward, terminated, truncated, env_done = step(self.actions[t])
             self.reward[t].copy_(reward)
             self.terminated[t].copy_(terminated)
             self.truncated[t].copy_(truncated)
             self.env_done[t].copy_(env_done)
+            if rnd is not None:
+                rnd.after_step()
         if self.global_state is not None:
             self.global_state[self.horizon].copy_(vec.global_state)
         if self.per_agent:
-            self.obs_block[self.horizon].copy_(vec.obs)
+            if per is None:
+                self.obs_block[self.horizon].copy_(vec.obs)
+            else:
+                per.sense(out=self.obs_block[self.horizon])
             self.critic.value(self.obs_block, out=self.value)
         elif self.critic is not None:
             self.critic.value(self.global_state, out=self.value)
