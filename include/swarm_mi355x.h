@@ -625,6 +625,55 @@ int swarm_sense(const swarm_sense_args_t* args, void* hip_stream);
 const char* swarm_perturb_last_error(void);
 
 /*
+ * Rollout fragments as one replayed graph (csrc/swarm_rollout.hip): sampling with the Philox counter
+ * in device memory, and the per-step copies of a fragment in one launch.  Both are one async launch
+ * on hip_stream, allocate nothing, do not synchronise, use no atomics and repeat bit for bit;
+ * errors via swarm_rollout_last_error, before any launch.
+ */
+#define SWARM_ROLLOUT_MAX_ACT 6        /* act_dim: the actors' out_dim / 2 */
+#define SWARM_ROLLOUT_MAX_SEGMENTS 8   /* segments of one record launch */
+
+/*
+ * actions [rows, A] from logits [rows, 2A] = [mean | log_std], A = act_dim in 1..6:
+ *     counter = (counter_dev ? *counter_dev : 0) + counter_add      (64-bit: the low word's carry
+ *               goes into the high word; the sum wraps at 2^64)
+ *     z_0..5  = the normals of row r from Philox(seed; r, counter), as SWARM_POLICY_ACT_SAMPLE draws them
+ *     actions[r, k] = logits[r, k] + expf(logits[r, A + k]) * z_k   (f32, the product rounded first)
+ * the expression and order of swarm_policy_forward and swarm_attn_policy_forward in
+ * SWARM_POLICY_ACT_SAMPLE, so for the logits those write, the same seed and the same counter this
+ * gives their actions bit for bit.  counter_dev is a device pointer to one 64-bit word (8-byte
+ * aligned), read when the kernel runs: a captured launch follows the word from replay to replay.
+ * counter_dev NULL: the counter is counter_add.  rows == 0 is a no-op.  One lane per row.
+ */
+int swarm_rollout_sample(const float* logits, long long rows, int act_dim, unsigned long long seed,
+                         const unsigned long long* counter_dev, unsigned long long counter_add, float* actions,
+                         void* hip_stream);
+
+typedef struct swarm_rollout_segment {
+  const void* src;   /* device */
+  void* dst;         /* device; NULL: the segment is skipped */
+  uint64_t bytes;    /* 0: the segment is skipped */
+} swarm_rollout_segment_t;
+
+/*
+ * Copy every segment, dst[0, bytes) = src[0, bytes), in one launch: nothing outside [dst, dst + bytes)
+ * is written.  Any alignment: a segment whose src and dst are both 16-byte aligned moves in 16-byte
+ * loads and stores (and a tail), one whose src and dst are both 4-byte aligned in 4-byte ones, any
+ * other byte by byte.  The segments of one call must not overlap each other, and no dst range may
+ * overlap any src range: the order in which bytes move is not defined.  count == 0, or every segment
+ * skipped, is a no-op.
+ */
+typedef struct swarm_rollout_record {
+  int32_t count;     /* 0 .. SWARM_ROLLOUT_MAX_SEGMENTS */
+  int32_t reserved;
+  swarm_rollout_segment_t segments[SWARM_ROLLOUT_MAX_SEGMENTS];
+} swarm_rollout_record_t;
+
+int swarm_rollout_record(const swarm_rollout_record_t* record, void* hip_stream);
+
+const char* swarm_rollout_last_error(void);
+
+/*
  * PPO loss head (csrc/swarm_ppo.hip): RLlib's PPOTorchPolicy.loss over a collected fragment, value
  * and gradient in one pass.  Rows are grouped by env-row: an env-row is one (t, e) with its N
  * consecutive agent rows (the collector's [T,E,N,...] flatten); values are per env-row.

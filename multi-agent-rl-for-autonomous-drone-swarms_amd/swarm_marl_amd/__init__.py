@@ -7,17 +7,19 @@ Host side of the C-ABI in include/swarm_mi355x.h.  `VecSwarm` is the batched ten
 on the device, `AttentionActor` its trainable torch module.  `AgentValueMLP` (with `gae_agent`) is the
 per-agent critic of the reference's multi-agent and single-agent PPO set-ups.  `Perturbation` (with
 `noise_spec`) is the control delay, thrust noise and sensing noise of the domain-randomisation recipe.
+`RolloutCollector(..., graph=True)` replays a whole fragment as one captured graph (`rollout_sample`,
+`rollout_record`: the device-counter sampling and the fused per-step copies it is built on).
 """
 from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .envs.common import DroneEnvConfig
 from .perturbation import Perturbation, noise_spec
 from .ppo import PPOLearner, masked_moments, ppo_loss
-from .rollout import RolloutCollector, gae, gae_agent, gaussian_logp
+from .rollout import RolloutCollector, gae, gae_agent, gaussian_logp, rollout_record, rollout_sample
 from .value import AgentValueMLP
 from .vec_env import VecSwarm
 
 __all__ = ["AgentValueMLP", "AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner",
            "Perturbation", "RolloutCollector", "VecSwarm", "gae", "gae_agent", "gaussian_logp", "masked_moments",
-           "noise_spec", "ppo_loss"]
+           "noise_spec", "ppo_loss", "rollout_record", "rollout_sample"]
 __version__ = "0.1.0"

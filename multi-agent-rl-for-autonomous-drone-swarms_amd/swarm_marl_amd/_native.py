@@ -72,6 +72,8 @@ PERTURB_MAX_DELAY = 7
 PERTURB_MAX_AGENTS = 256
 PERTURB_MAX_K = 16
 PERTURB_MAX_MS = 5
+ROLLOUT_MAX_ACT = 6
+ROLLOUT_MAX_SEGMENTS = 8
 
 # every symbol include/swarm_mi355x.h declares
 EXPORTED_SYMBOLS = (
@@ -84,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "swarm_env_cfg_set", "swarm_env_cfg_set_drones",
     "swarm_value_packed_bytes", "swarm_value_pack", "swarm_value_forward", "swarm_gae_agent", "swarm_value_last_error",
     "swarm_actuate", "swarm_sense", "swarm_perturb_last_error",
+    "swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
     "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
@@ -95,6 +98,7 @@ PPO_SYMBOLS = EXPORTED_SYMBOLS[-3:]
 ATTN_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_attn_"))  # csrc/swarm_attn.hip
 VALUE_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_value_")) + ("swarm_gae_agent",)  # csrc/swarm_value.hip
 PERTURB_SYMBOLS = ("swarm_actuate", "swarm_sense", "swarm_perturb_last_error")  # csrc/swarm_perturb.hip
+GRAPH_SYMBOLS = ("swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error")  # csrc/swarm_rollout.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 
 
@@ -219,6 +223,17 @@ class SwarmSenseArgs(ctypes.Structure):
                 ("obs", "active", "position_noise_std", "velocity_noise_std", "obstacle_noise_std", "step_count",
                  "episode", "out")] + [("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64)] + [
         (name, ctypes.c_int32) for name in ("num_envs", "num_drones", "neighbor_k", "sensed_obstacles")]
+
+
+class SwarmRolloutSegment(ctypes.Structure):
+    """swarm_rollout_segment_t."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_uint64)]
+
+
+class SwarmRolloutRecord(ctypes.Structure):
+    """swarm_rollout_record_t."""
+    _fields_ = [("count", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("segments", SwarmRolloutSegment * ROLLOUT_MAX_SEGMENTS)]
 
 
 class SwarmPpoArgs(ctypes.Structure):
@@ -350,6 +365,14 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.swarm_sense.argtypes = [ctypes.POINTER(SwarmSenseArgs), vp]
         lib.swarm_perturb_last_error.restype = ctypes.c_char_p
         lib.swarm_perturb_last_error.argtypes = []
+    if path is None or all(hasattr(lib, name) for name in GRAPH_SYMBOLS):
+        lib.swarm_rollout_sample.restype = ctypes.c_int
+        lib.swarm_rollout_sample.argtypes = [vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_ulonglong, vp,
+                                             ctypes.c_ulonglong, vp, vp]
+        lib.swarm_rollout_record.restype = ctypes.c_int
+        lib.swarm_rollout_record.argtypes = [ctypes.POINTER(SwarmRolloutRecord), vp]
+        lib.swarm_rollout_last_error.restype = ctypes.c_char_p
+        lib.swarm_rollout_last_error.argtypes = []
     if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
         lib.swarm_masked_moments.restype = ctypes.c_int
         lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -368,7 +391,7 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 # the component whose last-error string explains a return code (`check`'s `which`)
 LAST_ERROR = {"policy": "swarm_policy_last_error", "attn": "swarm_attn_policy_last_error",
               "eval": "swarm_eval_last_error", "critic": "swarm_critic_last_error", "ppo": "swarm_ppo_last_error",
-              "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error"}
+              "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error", "rollout": "swarm_rollout_last_error"}
 
 
 def check(rc: int, lib: ctypes.CDLL | None = None, which: str | None = None) -> None:

@@ -30,8 +30,17 @@ too, for the per-agent critic) and the step goes through `perturb.step`; actions
 policy's own, and global_state stays true (the centralized critic is privileged).  With
 `randomizer=` (a `DomainRandomizer`) its `after_step()` runs after every step of the fragment, so
 envs that reset inside one get fresh next-episode draws.  Both stay on the device.
+
+With `graph=True` the whole fragment is one captured graph, replayed by every
+`collect()`: per step the policy in mean mode, `swarm_rollout_sample` (the Philox counter is read from
+a device word the collector sets before the replay, plus the step index), `actuate` with a
+perturbation, the env step and ONE `swarm_rollout_record` launch for every copy of the step, then the
+critic, log-prob and GAE launches.  The fragments are bit for bit those of the eager collector with the
+same seed and counter.  Not with a randomizer, env groups or packed_io batches.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -108,6 +117,56 @@ def gae(reward: torch.Tensor, value: torch.Tensor, terminated: torch.Tensor, tru
     return advantage, value_target
 
 
+def rollout_sample(logits: torch.Tensor, actions: torch.Tensor, *, seed: int = 0, counter: int = 0,
+                   counter_dev: torch.Tensor | None = None) -> torch.Tensor:
+    """actions [..., A] = mean + exp(log_std) * N(0, 1) from logits [..., 2A] (swarm_rollout_sample):
+    the actors' draw and arithmetic, so their logits give their sampled actions bit for bit.  The
+    Philox counter is `counter`, plus the word of `counter_dev` (a one-element int64 device tensor,
+    read when the kernel runs) if given.  One launch, async on the current stream."""
+    if not isinstance(actions, torch.Tensor) or actions.dim() < 1 or actions.shape[-1] < 1:
+        raise ValueError("actions must be a tensor [..., A]")
+    adim = int(actions.shape[-1])
+    lead = tuple(actions.shape[:-1])
+    _check("actions", actions, lead + (adim,), _F32)
+    _check("logits", logits, lead + (2 * adim,), _F32, actions.device)
+    if counter_dev is not None:
+        _check("counter_dev", counter_dev, (1,), (torch.int64,), actions.device)
+    lib = nat.load_library()
+    nat.check(lib.swarm_rollout_sample(logits.data_ptr(), actions.numel() // adim, adim, int(seed) & (2**64 - 1),
+                                       None if counter_dev is None else counter_dev.data_ptr(),
+                                       int(counter) & (2**64 - 1), actions.data_ptr(), _stream(actions.device)),
+              lib, which="rollout")
+    return actions
+
+
+def rollout_record(pairs) -> None:
+    """dst.copy_(src) for up to 8 (src, dst) pairs of contiguous device tensors of equal byte size, in
+    one launch (swarm_rollout_record), async on the current stream; a pair whose dst is None is
+    skipped.  The tensors must not overlap."""
+    pairs = list(pairs)
+    if len(pairs) > nat.ROLLOUT_MAX_SEGMENTS:
+        raise ValueError(f"at most {nat.ROLLOUT_MAX_SEGMENTS} pairs per launch, got {len(pairs)}")
+    rec = nat.SwarmRolloutRecord()
+    dev = None
+    for src, dst in pairs:
+        if dst is None:
+            continue
+        for name, x in (("src", src), ("dst", dst)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or not x.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous device tensor")
+        nbytes = src.numel() * src.element_size()
+        if nbytes != dst.numel() * dst.element_size() or src.device != dst.device or (dev or src.device) != src.device:
+            raise ValueError("src and dst must hold the same number of bytes on one device")
+        dev = src.device
+        seg = rec.segments[rec.count]
+        seg.src, seg.dst, seg.bytes = src.data_ptr(), dst.data_ptr(), nbytes
+        rec.count += 1
+    if rec.count == 0:
+        return
+    lib = nat.load_library()
+    nat.check(lib.swarm_rollout_record(ctypes.byref(rec), _stream(dev)), lib, which="rollout")
+
+
 def gae_agent(*args, **kw):
     """`gae` with a per-agent value [T+1, E, N]: gae(..., per_agent=True)."""
     return gae(*args, per_agent=True, **kw)
@@ -124,11 +183,16 @@ class RolloutCollector:
       global_state [T+1,E,G] and value [T+1,E] (row t: before step t; row T: after the last step).
     With an `AgentValueMLP` as `critic`: value [T+1,E,N], and obs is the first-T view of `obs_block`
     [T+1,E,N,D] (row T: the obs after the last step); global_state only if the env has one.
+
+    graph=True: `collect()` replays one captured graph per mode (sampled, deterministic), captured at
+    the mode's first call and again when a buffer it baked in has moved (`captures` counts them;
+    weights loaded in place keep their graph).  `counter` is read and advanced as in eager mode.
     """
 
     def __init__(self, vec: VecSwarm, policy: PolicyMLP | AttentionPolicy, critic: CriticMLP | AgentValueMLP | None = None, *,
                  horizon: int,
-                 gamma: float = 0.99, lam: float = 0.95, seed: int = 0, perturb=None, randomizer=None):
+                 gamma: float = 0.99, lam: float = 0.95, seed: int = 0, perturb=None, randomizer=None,
+                 graph: bool = False):
         t = int(horizon)
         if t < 1:
             raise ValueError(f"horizon must be >= 1, got {horizon}")
@@ -153,11 +217,26 @@ class RolloutCollector:
         for name, hook in (("perturb", perturb), ("randomizer", randomizer)):
             if hook is not None and hook.vec is not vec:
                 raise ValueError(f"{name} belongs to another VecSwarm than the collector's")
+        if graph:
+            if randomizer is not None:
+                raise ValueError("graph=True does not take a randomizer: its after_step draws with a torch generator "
+                                 "and allocates, which a replayed graph cannot do")
+            if vec.groups != 1:
+                raise ValueError(f"graph=True needs a VecSwarm with one env group, got {vec.groups}: a grouped step "
+                                 "forks streams, the captured fragment is one chain on one stream")
+            if vec.packed_io:
+                raise ValueError("graph=True needs a device-resident batch: packed_io / mapped batches (the dict-API "
+                                 "envs) are not supported")
+        self.graph = bool(graph)
+        self.captures = 0  # graphs captured so far (graph mode)
+        self._graphs: dict = {}  # deterministic -> (key, CUDAGraph)
         self.vec, self.policy, self.critic = vec, policy, critic
         self.perturb, self.randomizer = perturb, randomizer
         self.horizon, self.gamma, self.lam, self.seed = t, float(gamma), float(lam), int(seed)
         self.counter = 0  # policy steps taken: the Philox counter of the next one
         kw = dict(device=vec.device)
+        # graph mode: `counter` as the sample launches read it (two's complement of the u64)
+        self._counter_dev = torch.zeros((1,), dtype=torch.int64, **kw) if graph else None
         f32 = torch.float32
         out = policy.out_dim
         self.obs_block = torch.zeros((t + 1, e, n, d), dtype=f32, **kw) if self.per_agent else None
@@ -182,6 +261,8 @@ class RolloutCollector:
         """One fragment from the env's current state (reset the env before the first call).
         deterministic=True acts with the Gaussian mean (evaluation): logp is then the log-density
         at the mean."""
+        if self.graph:
+            return self._collect_graph(bool(deterministic))
         vec, pol, per, rnd = self.vec, self.policy, self.perturb, self.randomizer
         step = vec.step if per is None else per.step
         for t in range(self.horizon):
@@ -215,4 +296,96 @@ class RolloutCollector:
         gaussian_logp(self.logits, self.actions, out=self.logp)
         gae(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid, gamma=self.gamma,
             lam=self.lam, advantage=self.advantage, value_target=self.value_target, per_agent=self.per_agent)
+        return self._batch
+
+    # ------------------------------------------------------------------ graph mode
+    def _graph_key(self) -> tuple:
+        """The device addresses (and switches) a captured fragment bakes in."""
+        vec, per = self.vec, self.perturb
+        owner = getattr(vec, "_eval_owner", None)
+        if owner is not None and owner.fused:
+            raise ValueError("graph=True cannot step an env with a fused EvalTracker attached: a captured step would "
+                             "replay its capture-time update index (detach() it)")
+        ts = [*vec.state_dict().values(), vec.obs, vec.reward, vec.terminated, vec.truncated, vec.env_done,
+              vec.global_state, vec.dist_goal, vec.info_flags, vec.work, vec.env_cfg, vec.env_cfg_next,
+              self.policy.weights, None if self.critic is None else self.critic.weights]
+        key = [None if x is None else x.data_ptr() for x in ts]
+        if per is not None:
+            key += [bool(per.enabled), per.ring.data_ptr(), per.eff.data_ptr(), per.delay.data_ptr(),
+                    per.thrust_noise_std.data_ptr(), per.position_noise_std.data_ptr(),
+                    per.velocity_noise_std.data_ptr(), per.obstacle_distance_noise_std.data_ptr()]
+        return tuple(key)
+
+    def _post(self) -> None:
+        """What follows the steps of a fragment: values, log-probs, GAE."""
+        if self.per_agent:
+            self.critic.value(self.obs_block, out=self.value)
+        elif self.critic is not None:
+            self.critic.value(self.global_state, out=self.value)
+        gaussian_logp(self.logits, self.actions, out=self.logp)
+        gae(self.reward, self.value, self.terminated, self.truncated, self.env_done, self.valid, gamma=self.gamma,
+            lam=self.lam, advantage=self.advantage, value_target=self.value_target, per_agent=self.per_agent)
+
+    def _issue(self, deterministic: bool) -> None:
+        """The launches of one fragment in graph mode, on the current stream."""
+        vec, pol, T = self.vec, self.policy, self.horizon
+        per = self.perturb if self.perturb is not None and self.perturb.enabled else None
+        step = vec.step if per is None else per.step
+        gs = self.global_state
+
+        def obs_row(t):  # the obs row step t - 1 leaves behind, or None
+            if t < T:
+                return self.obs[t]
+            return self.obs_block[T] if self.per_agent else None
+
+        rollout_record([(vec.active, self.valid[0]), (vec.obs, None if per is not None else self.obs[0]),
+                        (vec.global_state, None if gs is None else gs[0])])
+        if per is not None:
+            per.sense(out=self.obs[0])
+        for t in range(T):
+            if deterministic:
+                pol.forward(self.obs[t], logits=self.logits[t], actions=self.actions[t])
+            else:
+                pol.forward(self.obs[t], logits=self.logits[t])
+                rollout_sample(self.logits[t], self.actions[t], seed=self.seed, counter=t, counter_dev=self._counter_dev)
+            step(self.actions[t])
+            nxt = obs_row(t + 1)
+            rollout_record([(vec.reward, self.reward[t]), (vec.terminated, self.terminated[t]),
+                            (vec.truncated, self.truncated[t]), (vec.env_done, self.env_done[t]),
+                            (vec.active, self.valid[t + 1] if t + 1 < T else None),
+                            (vec.obs, None if per is not None else nxt),
+                            (vec.global_state, None if gs is None else gs[t + 1])])
+            if per is not None and nxt is not None:
+                per.sense(out=nxt)
+        self._post()
+
+    def _warm(self) -> None:
+        """First eager launches of the kernels whose launchers set a function attribute
+        (hipFuncSetAttribute: the actors and the value towers) and of this unit's, before they are
+        captured.  They write only fragment buffers that the replay overwrites; the env step and
+        `actuate` change state and are captured cold, as bench.py captures the step."""
+        self.policy.forward(self.obs[0], logits=self.logits[0], actions=self.actions[0])
+        rollout_sample(self.logits[0], self.actions[0], seed=self.seed, counter=0, counter_dev=self._counter_dev)
+        rollout_record([(self.vec.reward, self.reward[0])])
+        if self.perturb is not None and self.perturb.enabled:
+            self.perturb.sense(out=self.obs[0])
+        self._post()
+
+    def _collect_graph(self, deterministic: bool) -> dict[str, torch.Tensor]:
+        key = self._graph_key()
+        held = self._graphs.get(deterministic)
+        if held is None or held[0] != key:
+            self._warm()
+            g = torch.cuda.CUDAGraph()
+            # capture issues nothing: the env state, the delay line and the counter stay as they are
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._issue(deterministic)
+            held = (key, g)
+            self._graphs[deterministic] = held
+            self.captures += 1
+        if not deterministic:
+            c = self.counter & (2**64 - 1)
+            self._counter_dev.fill_(c - 2**64 if c >= 2**63 else c)  # eager, outside the graph
+        held[1].replay()
+        self.counter += self.horizon
         return self._batch
