@@ -1,5 +1,6 @@
 """NumPy definition of the actuation and sensing perturbations (the arithmetic in
-include/swarm_mi355x.h), the yardstick of tests/test_perturb_cpu.py and tests/test_gpu_perturb.py.
+include/swarm_mi355x.h), the yardstick of tests/test_perturb_cpu.py, tests/test_gpu_perturb.py and
+tests/test_gpu_perturb_shapes.py.
 
 Noise: Philox4x32-10 (oracle.swarm_oracle.philox4x32_10) with key (seed lo, seed hi) on the counter
 (g, n | block << 16 | stream << 30, episode, step), g the low 32 bits of env_offset + e.  Normals are
@@ -104,7 +105,9 @@ class DelayLine:
 
 def sense(obs, active, sigma_p, sigma_v, sigma_o, step_count, episode, seed, env_offset, k, ms):
     """(ref [E,N,D] float64, bound [E,N,D] float64, touched [E,N,D] bool) for obs [E,N,D] f32.
-    Where touched is False the output is obs bit for bit (bound 0)."""
+    Where touched is False the output is obs bit for bit (bound 0).  A sigma may be None: the NULL
+    pointer of the ABI, no noise in that group, as a zero sigma."""
+    sigma_p, sigma_v, sigma_o = (0.0 if x is None else x for x in (sigma_p, sigma_v, sigma_o))
     obs = np.asarray(obs, np.float32)
     e, n, dim = obs.shape
     assert dim == 9 + 4 * k + 4 * ms

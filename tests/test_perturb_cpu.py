@@ -1,5 +1,7 @@
 """CPU: the perturbation layer's config mapping, the argument checks of its two C entry points (no
-launch: every call returns before touching the GPU) and the reference's delay draw.
+launch: every call returns before touching the GPU) and the reference's delay draw; then what
+tests/test_gpu_perturb_shapes.py rests on: the reference's eight-entry table with zero-probability
+entries, its delay line at ring sizes 3 and 8 against a literally indexed history, and a None sigma.
 
 tests/golden/domain_randomization_v1.yaml is the reference's configs/domain_randomization_v1.yaml.
 """
@@ -240,3 +242,84 @@ def test_reference_normals_are_standard():
                   ref.normals(5, 1, 3, 3, 1, 7, 11), ref.normals(5, 1, 3, 2, 0, 7, 11), ref.normals(5, 1, 3, 2, 1, 8, 11),
                   ref.normals(5, 1, 3, 2, 1, 7, 12)):
         assert not np.array_equal(base, other)
+
+
+# ---------------------------------------------------------------- what tests/test_gpu_perturb_shapes.py rests on
+FULL_VALUES = [5, 2, 7, 0, 3, 6, 1, 4]
+FULL_PROBS = [0, 0.2, 0, 0.3, 0.1, 0, 0.4, 0]
+
+
+def test_reference_eight_entry_table_with_zero_probabilities():
+    """cum has equal consecutive entries where a prob is 0; `first i with u < cum[i]` never lands on
+    one of those, whatever the order of the values."""
+    from swarm_marl_amd.perturbation import delay_cum
+    cum = ref.delay_cum(FULL_PROBS)
+    assert np.array_equal(cum, np.array([0, .2, .2, .5, .6, .6, 1, 1], np.float32))
+    assert np.array_equal(delay_cum(FULL_PROBS), cum)
+    e = 4096
+    g, ep = 77 + np.arange(e), np.arange(e)[::-1].copy()
+    d = ref.draw_delays(FREQ_SEED, FULL_VALUES, FULL_PROBS, g, ep)
+    # literally: the uniform of the header against cum, entry by entry
+    x0 = ref._words(FREQ_SEED, g, 0, 0, ref.STREAM_DELAY, ep, 0)[0]
+    u = (x0 >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    for i in range(e):
+        first = next(j for j in range(8) if u[i] < cum[j])
+        assert d[i] == FULL_VALUES[first] and FULL_PROBS[first] > 0
+    for v, p in zip(FULL_VALUES, FULL_PROBS):
+        count = int((d == v).sum())
+        assert (count == 0) if p == 0 else abs(count - e * p) <= 5 * np.sqrt(e * p * (1 - p)), (v, count)
+    assert np.all(ref.draw_delays(FREQ_SEED, [5], [1.0], g, ep) == 5)  # a single entry draws nothing
+
+
+@pytest.mark.parametrize("r", [3, 8])
+def test_reference_delay_line_against_a_literal_history(r):
+    """DelayLine with ring_slots 3 and 8: eff is the clipped command of d steps ago in the same
+    episode, zero before the episode's step d, with restarts, a start far from 0 and overrides above
+    R - 1 (clamped to R - 1)."""
+    e, n, steps = 5, 2, 3 * r + 2
+    values = [r - 1, 0, 1]
+    line = ref.DelayLine(e, n, values, [0.3, 0.3, 0.4], FREQ_SEED, env_offset=3, ring_slots=r)
+    assert line.ring.shape == (r, e, n, 3)
+    override = np.array([r - 1, -1, 7 + r, -1, 0], np.int32)
+    rng = np.random.default_rng(r)
+    sc = np.array([0, 2**31 - 40, 0, 1, 2], np.int64)
+    ep = rng.integers(0, 2**32, e).astype(np.uint32)
+    hist, zeroed, seen = [], 0, set()
+    for t in range(steps):
+        a = rng.uniform(-1.5, 1.5, (e, n, 3)).astype(np.float32)
+        delayed, want, bound, d = line.actuate(a, sc, ep, None, override)
+        assert d[0] == r - 1 and d[2] == r - 1 and d[4] == 0 and set(d.tolist()) <= set(values)
+        assert not bound.any() and np.array_equal(want, delayed.astype(np.float64))
+        hist.append((ep.copy(), sc.copy(), np.clip(a, np.float32(-1), np.float32(1))))
+        for i in range(e):
+            if d[i] <= sc[i] and t - d[i] >= 0:
+                p_ep, p_sc, p_c = hist[t - d[i]]
+                assert p_ep[i] == ep[i] and p_sc[i] == sc[i] - d[i]
+                assert np.array_equal(delayed[i], p_c[i]), (t, i)
+            elif d[i] > sc[i]:
+                zeroed += 1
+                assert not delayed[i].any()
+        seen |= set(d.tolist())
+        sc += 1
+        for i in (3, 4):
+            if sc[i] >= r + 1 + i:
+                sc[i], ep[i] = 0, rng.integers(0, 2**32)
+    assert zeroed > 0 and len(seen) >= 2
+
+
+def test_reference_sense_none_sigma_is_a_zero_sigma():
+    e, n, k, ms = 4, 3, 2, 1
+    rng = np.random.default_rng(0)
+    obs = rng.uniform(-3, 3, (e, n, 9 + 4 * k + 4 * ms)).astype(np.float32)
+    active = np.ones((e, n), np.uint8)
+    sig = [np.full(e, s, np.float32) for s in (0.1, 0.2, 0.3)]
+    sc, ep = np.arange(e), np.arange(e) + 5
+    full = ref.sense(obs, active, *sig, sc, ep, 9, 2, k, ms)
+    for null in ((0,), (1,), (2,), (0, 1, 2)):
+        none = ref.sense(obs, active, *[None if i in null else s for i, s in enumerate(sig)], sc, ep, 9, 2, k, ms)
+        zeros = [np.zeros(e, np.float32) if i in null else s for i, s in enumerate(sig)]
+        zero = ref.sense(obs, active, *zeros, sc, ep, 9, 2, k, ms)
+        for a, b in zip(none, zero):
+            assert np.array_equal(a, b)
+        assert none[2].sum() < full[2].sum()
+    assert not none[2].any() and np.array_equal(none[0], obs.astype(np.float64))
