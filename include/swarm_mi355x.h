@@ -864,6 +864,55 @@ int swarm_env_cfg_set(const swarm_params_t* p, const swarm_env_overrides_t* ov, 
 int swarm_env_cfg_set_drones(const swarm_params_t* p, const int32_t* drones, const uint8_t* env_mask,
                              swarm_env_cfg_t* cfg, void* hip_stream);
 
+/*
+ * Keyed domain randomisation (csrc/swarm_dr.hip): per-episode parameter records as a pure function
+ * of (seed, global env index, episode number), drawn and derived on the device by one async launch
+ * on hip_stream, one thread per env.  No allocation, no synchronisation, no atomics, no host state;
+ * every argument is a device pointer or a constant, so the launch can be captured, and repeating it
+ * on the same state rewrites the same bytes.  num_envs == 0 is a no-op.  Errors via
+ * swarm_dr_last_error, before any launch: a NULL p / table / episode / cfg, abi_version, num_envs < 0,
+ * an enabled parameter with lo <= 0 or lo > hi (or a NaN), dt enabled with
+ * dynamics == SWARM_DYN_POINTMASS_PHYSICS (the physics substeps are uniform).
+ *
+ * Env e of the launch is written iff mask == NULL || (mask[e] & mask_bits) != 0 (an [E] bool mask with
+ * mask_bits = 0xFF; swarm_out_t.env_done with mask_bits = SWARM_ENV_RESET).  For a written env, with
+ *     g  = (uint32)(p->env_offset + e)
+ *     ep = episode[e] + episode_add            (uint32, wrapping; episode[e] read when the kernel runs)
+ * parameter i (0 world_size, 1 dt, 2 max_speed, 3 max_accel, 4 obstacle_radius) takes word x = i & 3 of
+ * the Philox4x32-10 block with key (seed lo, seed hi) and counter words
+ *     (g, 3u << 30 | (i >> 2) << 16, ep, 0)
+ * — the perturbation layer's counter layout (above) with stream 3, which that layer does not use, so
+ * a seed shared with it never shares a block — and, in double, every operation rounded on its own
+ * (no fused multiply-add):
+ *     u     = ((x >> 8) + 0.5) * 2^-24                        (exact; 0 < u < 1)
+ *     value = base_i * (lo_i + (hi_i - lo_i) * u)             base_i the parameter's swarm_params_t value
+ * A parameter with enabled[i] == 0 is base_i itself and draws nothing.
+ *
+ * From the five values the record takes exactly the fields swarm_env_cfg_set derives from them, bit
+ * for bit as swarm_env_cfg_set writes them for the same five doubles: half_w, neg_half_w, width_w,
+ * dt, max_speed, max_accel, s_vmax, s_obst, s_phys_obst, max_speed_d, world_size.  max_steps,
+ * num_obstacles and num_drones of cfg[e] are NOT written: the randomiser owns only what it
+ * randomises, and what a curriculum, swarm_env_cfg_set or swarm_env_cfg_set_drones put there stays.
+ * Envs outside the mask keep all 64 bytes.
+ *
+ * With env_cfg[e] = record(episode[e]) and env_cfg_next[e] = record(episode[e] + 1) (episode_add 0
+ * and 1), a reset moves the next record in and increments episode[e]; one launch on env_cfg_next
+ * with episode_add = 1 over the envs that reset restores both equalities.
+ */
+#define SWARM_DR_PARAMS 5
+
+typedef struct swarm_dr_table {     /* index: 0 world_size, 1 dt, 2 max_speed, 3 max_accel, 4 obstacle_radius */
+  double lo[SWARM_DR_PARAMS], hi[SWARM_DR_PARAMS];  /* scale range of parameter i */
+  uint8_t enabled[SWARM_DR_PARAMS]; /* 0: the parameter keeps its swarm_params_t value */
+} swarm_dr_table_t;
+
+int swarm_env_cfg_randomize(const swarm_params_t* p, const swarm_dr_table_t* table, uint64_t seed,
+                            const uint32_t* episode /* [E] swarm_state_t.episode */, uint32_t episode_add,
+                            const uint8_t* mask /* [E] or NULL */, uint8_t mask_bits,
+                            swarm_env_cfg_t* cfg /* [E] */, void* hip_stream);
+
+const char* swarm_dr_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

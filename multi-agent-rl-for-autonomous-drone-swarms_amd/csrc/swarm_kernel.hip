@@ -4574,6 +4574,7 @@ SWARM_PICK_DECL(3) { return pick_lm<KIND_AUX, DYN_PHYS>(lm, ks, msl); }
 #endif
 
 #if SWARM_HAS_HOST
+#include "swarm_env_cfg.h"  // s_threshold_dev, shared with swarm_dr.hip
 namespace {
 thread_local char g_err[512] = "";
 
@@ -4945,22 +4946,7 @@ int launch(int mode, const swarm_params_t* p, const swarm_state_t* s, const floa
   return SWARM_OK;
 }
 
-// ---- per-env parameter records (swarm_env_cfg_set)
-// s_threshold on the device: the same search with IEEE sqrt (llvm.sqrt) and one-ulp steps on
-// the bit pattern (every argument here is finite and >= 0, so the patterns are ordered).
-__device__ float s_threshold_dev(float T) {
-  if (!(T >= 0.0f)) return -1.0f;
-  if (__builtin_isinf(T)) return __builtin_inff();
-  float s = T * T;
-  while (s > 0.0f && __builtin_sqrtf(s) > T) s = __uint_as_float(__float_as_uint(s) - 1u);
-  for (;;) {
-    const float nx = __uint_as_float(__float_as_uint(s) + 1u);
-    if (__builtin_isinf(nx) || __builtin_sqrtf(nx) > T) break;
-    s = nx;
-  }
-  return s;
-}
-
+// ---- per-env parameter records (swarm_env_cfg_set; s_threshold_dev: swarm_env_cfg.h)
 struct EnvCfgBase {
   int E, M, max_steps;
   double world_size, dt, max_speed, max_accel, obstacle_radius, collision_radius, drone_contact_radius;

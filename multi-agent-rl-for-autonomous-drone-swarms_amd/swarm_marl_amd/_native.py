@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = (
     "swarm_value_packed_bytes", "swarm_value_pack", "swarm_value_forward", "swarm_gae_agent", "swarm_value_last_error",
     "swarm_actuate", "swarm_sense", "swarm_perturb_last_error",
     "swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error",
+    "swarm_env_cfg_randomize", "swarm_dr_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
     "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
@@ -99,7 +100,9 @@ ATTN_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_attn_"))
 VALUE_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_value_")) + ("swarm_gae_agent",)  # csrc/swarm_value.hip
 PERTURB_SYMBOLS = ("swarm_actuate", "swarm_sense", "swarm_perturb_last_error")  # csrc/swarm_perturb.hip
 GRAPH_SYMBOLS = ("swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error")  # csrc/swarm_rollout.hip
+DR_SYMBOLS = ("swarm_env_cfg_randomize", "swarm_dr_last_error")  # csrc/swarm_dr.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
+DR_PARAMS = ("world_size", "dt", "max_speed", "max_accel", "obstacle_radius")  # swarm_dr_table_t's index order
 
 
 class NativeLibraryError(RuntimeError):
@@ -223,6 +226,12 @@ class SwarmSenseArgs(ctypes.Structure):
                 ("obs", "active", "position_noise_std", "velocity_noise_std", "obstacle_noise_std", "step_count",
                  "episode", "out")] + [("seed", ctypes.c_uint64), ("env_offset", ctypes.c_int64)] + [
         (name, ctypes.c_int32) for name in ("num_envs", "num_drones", "neighbor_k", "sensed_obstacles")]
+
+
+class SwarmDrTable(ctypes.Structure):
+    """swarm_dr_table_t: scale range and switch of each DR_PARAMS entry."""
+    _fields_ = [("lo", ctypes.c_double * len(DR_PARAMS)), ("hi", ctypes.c_double * len(DR_PARAMS)),
+                ("enabled", ctypes.c_uint8 * len(DR_PARAMS))]
 
 
 class SwarmRolloutSegment(ctypes.Structure):
@@ -373,6 +382,12 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
         lib.swarm_rollout_record.argtypes = [ctypes.POINTER(SwarmRolloutRecord), vp]
         lib.swarm_rollout_last_error.restype = ctypes.c_char_p
         lib.swarm_rollout_last_error.argtypes = []
+    if path is None or all(hasattr(lib, name) for name in DR_SYMBOLS):
+        lib.swarm_env_cfg_randomize.restype = ctypes.c_int
+        lib.swarm_env_cfg_randomize.argtypes = [P, ctypes.POINTER(SwarmDrTable), ctypes.c_uint64, vp, ctypes.c_uint32,
+                                                vp, ctypes.c_uint8, vp, vp]
+        lib.swarm_dr_last_error.restype = ctypes.c_char_p
+        lib.swarm_dr_last_error.argtypes = []
     if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
         lib.swarm_masked_moments.restype = ctypes.c_int
         lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -391,7 +406,8 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 # the component whose last-error string explains a return code (`check`'s `which`)
 LAST_ERROR = {"policy": "swarm_policy_last_error", "attn": "swarm_attn_policy_last_error",
               "eval": "swarm_eval_last_error", "critic": "swarm_critic_last_error", "ppo": "swarm_ppo_last_error",
-              "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error", "rollout": "swarm_rollout_last_error"}
+              "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error", "rollout": "swarm_rollout_last_error",
+              "dr": "swarm_dr_last_error"}
 
 
 def check(rc: int, lib: ctypes.CDLL | None = None, which: str | None = None) -> None:

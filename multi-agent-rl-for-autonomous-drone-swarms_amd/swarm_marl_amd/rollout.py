@@ -36,7 +36,9 @@ With `graph=True` the whole fragment is one captured graph, re
 a device word the collector sets before the replay, plus the step index), `actuate` with a
 perturbation, the env step and ONE `swarm_rollout_record` launch for every copy of the step, then the
 critic, log-prob and GAE launches.  The fragments are bit for bit those of the eager collector with the
-same seed and counter.  Not with a randomizer, env groups or packed_io batches.
+same seed and counter.  A keyed randomizer (`DomainRandomizer(keyed=True)`) is captured
+too: its `after_step()` is one launch after each step's record launch, where the eager loop calls it.
+Not with a generator-mode randomizer, env groups or packed_io batches.
 """
 from __future__ import annotations
 
@@ -218,7 +220,7 @@ class RolloutCollector:
             if hook is not None and hook.vec is not vec:
                 raise ValueError(f"{name} belongs to another VecSwarm than the collector's")
         if graph:
-            if randomizer is not None:
+            if randomizer is not None and not getattr(randomizer, "keyed", False):
                 raise ValueError("graph=True does not take a randomizer: its after_step draws with a torch generator "
                                  "and allocates, which a replayed graph cannot do")
             if vec.groups != 1:
@@ -314,6 +316,8 @@ class RolloutCollector:
             key += [bool(per.enabled), per.ring.data_ptr(), per.eff.data_ptr(), per.delay.data_ptr(),
                     per.thrust_noise_std.data_ptr(), per.position_noise_std.data_ptr(),
                     per.velocity_noise_std.data_ptr(), per.obstacle_distance_noise_std.data_ptr()]
+        if self.randomizer is not None:  # keyed: the launch bakes in its seed and table (the records are above)
+            key.append(self.randomizer.graph_key())
         return tuple(key)
 
     def _post(self) -> None:
@@ -331,7 +335,7 @@ class RolloutCollector:
         vec, pol, T = self.vec, self.policy, self.horizon
         per = self.perturb if self.perturb is not None and self.perturb.enabled else None
         step = vec.step if per is None else per.step
-        gs = self.global_state
+        gs, rnd = self.global_state, self.randomizer
 
         def obs_row(t):  # the obs row step t - 1 leaves behind, or None
             if t < T:
@@ -355,6 +359,8 @@ class RolloutCollector:
                             (vec.active, self.valid[t + 1] if t + 1 < T else None),
                             (vec.obs, None if per is not None else nxt),
                             (vec.global_state, None if gs is None else gs[t + 1])])
+            if rnd is not None:
+                rnd.after_step()
             if per is not None and nxt is not None:
                 per.sense(out=nxt)
         self._post()
@@ -369,6 +375,8 @@ class RolloutCollector:
         rollout_record([(self.vec.reward, self.reward[0])])
         if self.perturb is not None and self.perturb.enabled:
             self.perturb.sense(out=self.obs[0])
+        if self.randomizer is not None:  # rewrites what the records hold: the keyed draw repeats bit for bit
+            self.randomizer.after_step()
         self._post()
 
     def _collect_graph(self, deterministic: bool) -> dict[str, torch.Tensor]:
