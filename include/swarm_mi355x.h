@@ -328,6 +328,91 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
 const char* swarm_policy_last_error(void);
 
 /*
+ * Training the SWARM_POLICY_BF16 actor on the device (csrc/swarm_train.hip): float32 master weights
+ * stay with the caller (torch parameters under Adam); the forward is swarm_policy_forward itself, the
+ * backward below runs on the same bf16 MFMA operands with f32 accumulation, and a device packer
+ * rebuilds the inference blob from the masters.  All calls are async on hip_stream, allocate nothing,
+ * read nothing back, use no atomics and launch grids that depend on `rows` only (never on the
+ * device's CU count), so a call repeats bit for bit.  Errors via swarm_policy_train_last_error,
+ * before any launch.  Limits are the bf16 policy's: in_dim 1..SWARM_POLICY_MAX_IN, out_dim even in
+ * 2..SWARM_POLICY_MAX_OUT, anything else SWARM_ELIMIT.
+ *
+ * Notation: bf(v) is v rounded to bf16, round to nearest even.  x~ is the obs row widened with
+ * x~[in_dim] = 1 (the bias column).  W1~ = [W1 | b1].  Every product below is of two bf16 values (exact
+ * in f32) and every sum is an f32 MFMA accumulation.
+ *
+ * swarm_policy_backward, per row r (obs must be finite; the weights too):
+ *     h1 = relu(bf(bf(W1~) bf(x~)))                  the inference kernel's h1: the same fragments, the
+ *     h2 = relu(bf(bf(W2) h1 + b2))                  same MFMA order, relu after the rounding
+ *     g  = bf(grad_logits[r])
+ *     dz2 = bf(bf(W3)^T g) where h2 > 0, else 0      16 terms per sum (m >= out_dim are zeros)
+ *     dz1 = bf(bf(W2)^T dz2) where h1 > 0, else 0    256 terms, o = 0..255 in 16 k-steps of 16
+ * and over the rows, in f32:
+ *     dW3[m][u] = sum_r g[m] h2[u]      db3[m] = sum_r g[m]
+ *     dW2[o][i] = sum_r dz2[o] h1[i]    db2[o] = sum_r dz2[o]
+ *     dW1[o][k] = sum_r dz1[o] bf(x[k]) db1[o] = sum_r dz1[o]     (db1 is column in_dim of dz1 x~^T)
+ * Reduction order of every one of those sums: rows are padded to a multiple of 32 (a padded row has
+ * g = 0: every dz of it is exactly 0); slab s holds rows [SWARM_TRAIN_SLAB s, SWARM_TRAIN_SLAB (s + 1));
+ * a slab's partial sum is one MFMA accumulator chain over its rows in ascending 16-row k-steps (the bias
+ * sums are the same chain against a B operand of ones); the result is partial 0 + partial 1 + ... in
+ * slab order.  So the longest chain of f32 additions behind an element is
+ *     L = SWARM_TRAIN_SLAB + nslabs - 1,   nslabs = ceil(rows / SWARM_TRAIN_SLAB)
+ * and |error| <= L 2^-24 sum|terms| against the exact sum of the same bf16 products.
+ * A row whose grad_logits are all zero adds exactly zero to every gradient (the collector writes zero
+ * obs rows for invalid agents and the loss head zero gradients).  rows == 0 is a no-op: nothing is
+ * written.  Gradients are written, not accumulated into.
+ *
+ * Launches: (a) h1, h2, dz2 and (b) dz1, one wave per 32-row tile, 8 waves per workgroup, at most
+ * SWARM_TRAIN_MAX_BLOCKS workgroups (further tiles in further passes); (c) three weight-gradient
+ * launches of one workgroup per slab; (d) the finalising sum, one thread per gradient element.
+ */
+#define SWARM_TRAIN_SLAB 1024        /* rows per weight-gradient slab */
+#define SWARM_TRAIN_MAX_BLOCKS 256   /* workgroups of the tile launches (a) and (b) */
+#define SWARM_TRAIN_MAX_ROWS (1LL << 28)  /* rows of one backward call (32-bit lane offsets); more: SWARM_ELIMIT */
+
+/* Bytes of the training workspace for backward calls of up to `rows` rows (negative SWARM_E* code for
+ * unsupported dims or rows < 0).  Its first bytes hold the packer's transposed blobs: the workspace a
+ * backward call is given must be the one the last swarm_policy_pack_device wrote. */
+long long swarm_policy_train_workspace_bytes(int in_dim, int out_dim, long long rows);
+
+/*
+ * Device packer, one launch.  Reads the six float32 master arrays (device memory, PyTorch layout:
+ * w1 [256,in], b1 [256], w2 [256,256], b2 [256], w3 [out,256], b3 [out]) and writes
+ *   - `weights` (device, swarm_policy_packed_bytes(in, out, SWARM_POLICY_BF16) bytes, 16-B aligned):
+ *     byte for byte what swarm_policy_pack writes for the same arrays — bf16 round to nearest even,
+ *     W1 with b1 in column `in`, W2 / W3 in the accumulator-chained k order, b2 / b3 in f32, zeros
+ *     in the padding.  Written in place: a swarm_policy_t pointing at it stays valid.
+ *   - the head of `workspace` (16-B aligned): bf(W2)^T and bf(W3)^T in MFMA-fragment order for
+ *     swarm_policy_backward.
+ */
+int swarm_policy_pack_device(int in_dim, int out_dim, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* w3, const float* b3, void* weights, void* workspace, void* hip_stream);
+
+typedef struct swarm_policy_backward_args {
+  const void* weights;       /* the SWARM_POLICY_BF16 blob (device, 16-B aligned) */
+  const float* obs;          /* [rows, in_dim] finite */
+  const float* grad_logits;  /* [rows, out_dim] */
+  void* workspace;           /* swarm_policy_train_workspace_bytes(.., rows) bytes, 16-B aligned, private
+                                to the call while it runs, head written by swarm_policy_pack_device */
+  float* dw1;                /* [256, in_dim] */
+  float* db1;                /* [256] */
+  float* dw2;                /* [256, 256] */
+  float* db2;                /* [256] */
+  float* dw3;                /* [out_dim, 256] */
+  float* db3;                /* [out_dim] */
+  uint16_t* h1;              /* optional stage outputs: bf16 bit patterns [rows, 256], row-major, natural */
+  uint16_t* h2;              /* unit order, 8-B aligned; NULL: nothing extra is written */
+  uint16_t* dz2;
+  uint16_t* dz1;
+  long long rows;
+  int32_t in_dim, out_dim;
+} swarm_policy_backward_args_t;
+
+int swarm_policy_backward(const swarm_policy_backward_args_t* args, void* hip_stream);
+
+const char* swarm_policy_train_last_error(void);
+
+/*
  * On-device attention actor: the reference's CentralizedCriticModel(use_attention=True) actor
  * (src/swarm_marl/training/models.py:104-137, scripts/train_attention.py), eval mode.  For one
  * observation row x of width D = 9 + 4K + 4Ms, own = x[0:9], nb_j = x[9+4j : 13+4j] (j < K),

@@ -9,7 +9,9 @@ per-agent critic of the reference's multi-agent and single-agent PPO set-ups.  `
 `noise_spec`) is the control delay, thrust noise and sensing noise of the domain-randomisation recipe.
 `RolloutCollector(..., graph=True)` replays a whole fragment as one captured graph (`rollout_sample`,
 `rollout_record`: the device-counter sampling and the fused per-step copies it is built on).
+`ActorTrainer` trains the bf16 actor on the device (`PPOLearner(..., backend="hip")`).
 """
+from .actor_train import ActorTrainer
 from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .envs.common import DroneEnvConfig
@@ -19,7 +21,7 @@ from .rollout import RolloutCollector, gae, gae_agent, gaussian_logp, rollout_re
 from .value import AgentValueMLP
 from .vec_env import VecSwarm
 
-__all__ = ["AgentValueMLP", "AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner",
+__all__ = ["ActorTrainer", "AgentValueMLP", "AttentionActor", "AttentionPolicy", "CriticMLP", "DroneEnvConfig", "PPOLearner",
            "Perturbation", "RolloutCollector", "VecSwarm", "gae", "gae_agent", "gaussian_logp", "masked_moments",
            "noise_spec", "ppo_loss", "rollout_record", "rollout_sample"]
 __version__ = "0.1.0"

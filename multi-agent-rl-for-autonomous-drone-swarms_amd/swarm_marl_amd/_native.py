@@ -74,6 +74,9 @@ PERTURB_MAX_K = 16
 PERTURB_MAX_MS = 5
 ROLLOUT_MAX_ACT = 6
 ROLLOUT_MAX_SEGMENTS = 8
+TRAIN_SLAB = 1024        # SWARM_TRAIN_SLAB: rows per weight-gradient slab
+TRAIN_MAX_BLOCKS = 256   # SWARM_TRAIN_MAX_BLOCKS: workgroups of the backward's tile launches
+TRAIN_MAX_ROWS = 1 << 28
 
 # every symbol include/swarm_mi355x.h declares
 EXPORTED_SYMBOLS = (
@@ -88,6 +91,8 @@ EXPORTED_SYMBOLS = (
     "swarm_actuate", "swarm_sense", "swarm_perturb_last_error",
     "swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error",
     "swarm_env_cfg_randomize", "swarm_dr_last_error",
+    "swarm_policy_train_workspace_bytes", "swarm_policy_pack_device", "swarm_policy_backward",
+    "swarm_policy_train_last_error",
     "swarm_critic_packed_bytes", "swarm_critic_pack", "swarm_critic_forward", "swarm_critic_last_error",
     "swarm_gaussian_logp", "swarm_gae",
     "swarm_masked_moments", "swarm_ppo_loss", "swarm_ppo_last_error",
@@ -101,6 +106,8 @@ VALUE_SYMBOLS = tuple(s for s in EXPORTED_SYMBOLS if s.startswith("swarm_value_"
 PERTURB_SYMBOLS = ("swarm_actuate", "swarm_sense", "swarm_perturb_last_error")  # csrc/swarm_perturb.hip
 GRAPH_SYMBOLS = ("swarm_rollout_sample", "swarm_rollout_record", "swarm_rollout_last_error")  # csrc/swarm_rollout.hip
 DR_SYMBOLS = ("swarm_env_cfg_randomize", "swarm_dr_last_error")  # csrc/swarm_dr.hip
+TRAIN_SYMBOLS = ("swarm_policy_train_workspace_bytes", "swarm_policy_pack_device", "swarm_policy_backward",
+                 "swarm_policy_train_last_error")  # csrc/swarm_train.hip
 ENV_CFG_BYTES = 64  # sizeof(swarm_env_cfg_t)
 DR_PARAMS = ("world_size", "dt", "max_speed", "max_accel", "obstacle_radius")  # swarm_dr_table_t's index order
 
@@ -179,6 +186,14 @@ class SwarmOut(ctypes.Structure):
 class SwarmPolicy(ctypes.Structure):
     _fields_ = [("in_dim", ctypes.c_int32), ("out_dim", ctypes.c_int32), ("precision", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("weights", ctypes.c_void_p)]
+
+
+class SwarmPolicyBackwardArgs(ctypes.Structure):
+    """swarm_policy_backward_args_t."""
+    _fields_ = [(name, ctypes.c_void_p) for name in
+                ("weights", "obs", "grad_logits", "workspace", "dw1", "db1", "dw2", "db2", "dw3", "db3",
+                 "h1", "h2", "dz2", "dz1")] + [("rows", ctypes.c_longlong), ("in_dim", ctypes.c_int32),
+                                               ("out_dim", ctypes.c_int32)]
 
 
 class SwarmAttnPolicy(ctypes.Structure):
@@ -388,6 +403,15 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
                                                 vp, ctypes.c_uint8, vp, vp]
         lib.swarm_dr_last_error.restype = ctypes.c_char_p
         lib.swarm_dr_last_error.argtypes = []
+    if path is None or all(hasattr(lib, name) for name in TRAIN_SYMBOLS):
+        lib.swarm_policy_train_workspace_bytes.restype = ctypes.c_longlong
+        lib.swarm_policy_train_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]
+        lib.swarm_policy_pack_device.restype = ctypes.c_int
+        lib.swarm_policy_pack_device.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.swarm_policy_backward.restype = ctypes.c_int
+        lib.swarm_policy_backward.argtypes = [ctypes.POINTER(SwarmPolicyBackwardArgs), vp]
+        lib.swarm_policy_train_last_error.restype = ctypes.c_char_p
+        lib.swarm_policy_train_last_error.argtypes = []
     if path is None or all(hasattr(lib, name) for name in PPO_SYMBOLS):
         lib.swarm_masked_moments.restype = ctypes.c_int
         lib.swarm_masked_moments.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -407,7 +431,7 @@ def load_library(path: str | os.PathLike | None = None) -> ctypes.CDLL:
 LAST_ERROR = {"policy": "swarm_policy_last_error", "attn": "swarm_attn_policy_last_error",
               "eval": "swarm_eval_last_error", "critic": "swarm_critic_last_error", "ppo": "swarm_ppo_last_error",
               "value": "swarm_value_last_error", "perturb": "swarm_perturb_last_error", "rollout": "swarm_rollout_last_error",
-              "dr": "swarm_dr_last_error"}
+              "dr": "swarm_dr_last_error", "train": "swarm_policy_train_last_error"}
 
 
 def check(rc: int, lib: ctypes.CDLL | None = None, which: str | None = None) -> None:

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .actor_train import ActorTrainer
 from .attention import AttentionActor, AttentionPolicy
 from .critic import CriticMLP
 from .policy import PolicyMLP
@@ -174,12 +175,25 @@ class PPOLearner:
     With an `AgentValueMLP` as `critic` (the per-agent value tower of the reference's multi-agent and
     single-agent PPO set-ups) `value_net` is D -> 256 -> 256 -> 1 on the minibatch's obs rows, `ppo_loss`
     gets one value per agent row, and a fragment without `global_state` is accepted.
+
+    backend="hip" (needs a `PolicyMLP` of precision "bf16") trains the actor on the
+    device instead: the parameters under Adam are an `ActorTrainer`'s float32 masters, a minibatch's
+    logits come from the inference kernel itself as a leaf tensor, `loss.backward()` stops there and at
+    the value net, `trainer.backward` turns d loss / d logits into the masters' gradients, and after the
+    Adam step `trainer.push()` repacks the blob on the device — in place, so a captured collector keeps
+    its graph.  A bf16 collector is then exactly on-policy.  `policy.layers` is refreshed by one
+    device-to-host copy at the end of `update`.  The value net stays torch in either backend.
     """
 
     def __init__(self, policy: PolicyMLP, critic: CriticMLP | AgentValueMLP, *, lr: float = 3e-4, num_epochs: int = 10,
-                 minibatch_env_rows: int, kl_target: float = 0.01, seed: int = 0, **loss_kw):
+                 minibatch_env_rows: int, kl_target: float = 0.01, seed: int = 0, backend: str = "torch", **loss_kw):
         if not isinstance(policy, (PolicyMLP, AttentionPolicy)) or not isinstance(critic, (CriticMLP, AgentValueMLP)):
             raise ValueError("PPOLearner needs a PolicyMLP and a CriticMLP")
+        if backend not in ("torch", "hip"):
+            raise ValueError(f"backend must be 'torch' or 'hip', got {backend!r}")
+        if backend == "hip" and not (isinstance(policy, PolicyMLP) and policy.precision == "bf16"):
+            raise ValueError("backend='hip' trains a PolicyMLP of precision 'bf16' (not an AttentionPolicy, not f32 / f32x3)")
+        self.backend = backend
         self.per_agent = isinstance(critic, AgentValueMLP)
         if self.per_agent and critic.in_dim != policy.in_dim:
             raise ValueError(f"the per-agent critic takes {critic.in_dim} inputs, the policy's observations are "
@@ -198,10 +212,12 @@ class PPOLearner:
         self.kl_target = float(kl_target)
         self.kl_coeff = float(loss_kw.pop("kl_coeff", 0.2))
         self.loss_kw = loss_kw
-        self.actor = (AttentionActor.from_policy(policy).to(self.device) if isinstance(policy, AttentionPolicy)
-                      else _mlp(policy.layers, self.device))
+        self.trainer = ActorTrainer(policy) if backend == "hip" else None
+        self.actor = (None if self.trainer else AttentionActor.from_policy(policy).to(self.device)
+                      if isinstance(policy, AttentionPolicy) else _mlp(policy.layers, self.device))
         self.value_net = _mlp(critic.layers, self.device)
-        self.optimizer = torch.optim.Adam(list(self.actor.parameters()) + list(self.value_net.parameters()), lr=lr)
+        actor_params = self.trainer.parameters() if self.trainer else list(self.actor.parameters())
+        self.optimizer = torch.optim.Adam(actor_params + list(self.value_net.parameters()), lr=lr)
         self.generator = torch.Generator(device=self.device).manual_seed(int(seed))
         self._adv_moments = torch.empty(nat.PPO_MOMENTS, dtype=torch.float64, device=self.device)
         self._valid_moments = torch.empty(nat.PPO_MOMENTS, dtype=torch.float64, device=self.device)
@@ -262,7 +278,8 @@ class PPOLearner:
                 for k in cur:
                     torch.index_select(src[k], 0, idx, out=cur[k])
                 masked_moments(cur["advantage"], cur["valid"], out=self._valid_moments)
-                logits = self.actor(cur["obs"].view(m * n, d))
+                obs_mb = cur["obs"].view(m * n, d)
+                logits = self.trainer.logits(obs_mb).requires_grad_(True) if self.trainer else self.actor(obs_mb)
                 value = (self.value_net(cur["global_state"]).view(m) if g else
                          self.value_net(cur["obs"].view(m * n, d)).view(m * n))
                 loss, stats = ppo_loss(logits, value, behaviour_logits=cur["behaviour_logits"], actions=cur["actions"],
@@ -271,7 +288,11 @@ class PPOLearner:
                                        valid_moments=self._valid_moments, kl_coeff=self.kl_coeff, **self.loss_kw)
                 self.optimizer.zero_grad(set_to_none=True)
                 loss.backward()
+                if self.trainer:
+                    self.trainer.backward(obs_mb, logits.grad)
                 self.optimizer.step()
+                if self.trainer:
+                    self.trainer.push()
                 epochs[ep] += stats
         epochs /= nmb
         host = epochs.cpu().numpy()  # the update's one read of a device result
@@ -282,7 +303,9 @@ class PPOLearner:
             self.kl_coeff *= 0.5
         info["kl_coeff"] = self.kl_coeff
         info["epoch_total_loss"] = [float(v) for v in host[:, 1]]
-        if isinstance(self.policy, AttentionPolicy):
+        if self.trainer:
+            self.trainer.sync_policy()
+        elif isinstance(self.policy, AttentionPolicy):
             self.policy.load_params(*self.actor.split_state())
         else:
             self.policy.load_layers(_layers_of(self.actor))
