@@ -36,7 +36,7 @@ namespace {
 typedef const __attribute__((address_space(4))) float* cfloat_p;  // constant address space: scalar loads
 
 constexpr int EM = SWARM_ATTN_EMBED;    // 32
-constexpr int KS1 = 4;                  // layer-1 k-steps: [s 32 | own, obst, 1: <= 30, padded to 32]
+constexpr int KS1A = 4;                 // this trunk's layer-1 k-steps: [s 32 | own, obst, 1: <= 30, padded to 32]
 
 // f32 front-end block of the bf16 blob (float offsets)
 constexpr int FE_OWN_W = 0, FE_OWN_B = FE_OWN_W + EM * 9, FE_NB_W = FE_OWN_B + EM, FE_NB_B = FE_NB_W + EM * 4,
@@ -52,7 +52,7 @@ struct Bf16Layout {
     b2 = w3 + (size_t)KS2 * 2 * o * 16;
     b3 = b2 + H * 4;
     w1 = b3 + 32 * 4;
-    fe = w1 + (size_t)OB * KS1 * FRAG;
+    fe = w1 + (size_t)OB * KS1A * FRAG;
     total = fe + (size_t)FE_FLOATS * 4;
   }
 };
@@ -103,7 +103,7 @@ struct FwdArgs {
 // ---------------------------------------------------------------- bf16 kernel
 constexpr int LDS_W2 = 0;                    // LDS image: W2 fragments, then the layer-1 fragments
 constexpr int LDS_W1 = OB * KS2 * FRAG;      // 131072
-constexpr int LDS_BYTES = LDS_W1 + OB * KS1 * FRAG;  // 163840: the whole LDS of a CU
+constexpr int LDS_BYTES = LDS_W1 + OB * KS1A * FRAG;  // 163840: the whole LDS of a CU
 
 // The trunk over one 32-row tile: swarm_policy.hip's policy_mlp_bf16 (T = 1) with four layer-1
 // k-steps.  W1 and W2 fragments come from LDS; what no longer fits there — W3's fragments, b2, b3,
@@ -112,7 +112,7 @@ constexpr int LDS_BYTES = LDS_W1 + OB * KS1 * FRAG;  // 163840: the whole LDS of
 // accumulators start at zero) so that their loads have that block to land in.
 template <int MODE>
 __device__ __forceinline__ void trunk_tile(const FwdArgs& A, const unsigned char* lds, const Bf16Layout& L,
-                                           const unsigned char* gw, const bf16x8 (&xb)[KS1], int lane, int out,
+                                           const unsigned char* gw, const bf16x8 (&xb)[KS1A], int lane, int out,
                                            long long row, bool valid) {
   const int n = lane & 31, h = (lane >> 5) & 1;
   const bool w3lane = n < out;
@@ -131,8 +131,8 @@ __device__ __forceinline__ void trunk_tile(const FwdArgs& A, const unsigned char
   for (int ob = 0; ob < OB; ++ob) {
     f32x16 acc = f32x16{};
 #pragma unroll
-    for (int ks = 0; ks < KS1; ++ks)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1f[(ob * KS1 + ks) * 64], xb[ks], acc, 0, 0, 0);
+    for (int ks = 0; ks < KS1A; ++ks)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1f[(ob * KS1A + ks) * 64], xb[ks], acc, 0, 0, 0);
     h1[2 * ob] = pack8(acc, 0, true);
     h1[2 * ob + 1] = pack8(acc, 1, true);
     __builtin_amdgcn_sched_barrier(0);  // keep each out block's fragment reads inside it
@@ -318,7 +318,7 @@ attn_policy_bf16(const FwdArgs A) {
     // half-h columns.  permlane32_swap(a, b) exchanges lanes 32-63 of a with lanes 0-31 of b: with
     // a = the half-0 dword and b = the half-1 dword, a becomes tile 0's fragment dword (lanes 0-31
     // their own half 0, lanes 32-63 row n's half 1) and b tile 1's.
-    bf16x8 xb[2][KS1];
+    bf16x8 xb[2][KS1A];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       u32x4 f0, f1, g0, g1;
@@ -583,8 +583,6 @@ int swarm_attn_policy_pack(int neighbor_k, int sensed_obstacles, int out_dim, in
   }
   // ---- layer 1: row m of [F | W1 own | W1 obst | b1 + d | 0], F's columns in fragment order
   uint16_t* w1f = reinterpret_cast<uint16_t*>(base + L.w1);
-  uint16_t* w2f = reinterpret_cast<uint16_t*>(base + L.w2);
-  uint16_t* w3f = reinterpret_cast<uint16_t*>(base + L.w3);
   for (int m = 0; m < H; ++m) {
     const float* w1r = w->w1 + (size_t)m * in1;
     float rowv[64];
@@ -605,21 +603,11 @@ int swarm_attn_policy_pack(int neighbor_k, int sensed_obstacles, int out_dim, in
       }
       rowv[32 + t] = v;
     }
-    const int ob = m >> 5, nl = m & 31;
-    for (int k = 0; k < 64; ++k) {
-      const int ks = k >> 4, h = (k >> 3) & 1, j = k & 7;
-      w1f[((size_t)(ob * KS1 + ks) * 64 + 32 * h + nl) * 8 + j] = bf16_rne(rowv[k]);
-    }
-    for (int h = 0; h < 2; ++h)
-      for (int ks = 0; ks < KS2; ++ks)
-        for (int j = 0; j < 8; ++j)
-          w2f[((size_t)(ob * KS2 + ks) * 64 + 32 * h + nl) * 8 + j] = bf16_rne(w->w2[(size_t)m * H + chained_k(ks, h, j)]);
+    for (int k = 0; k < 64; ++k)  // natural k: k-step k >> 4, lane half (k >> 3) & 1, element k & 7
+      w1f[(size_t)frag_slot((m >> 5) * KS1A + (k >> 4), m & 31, (k >> 3) & 1) * 8 + (k & 7)] = bf16_rne(rowv[k]);
   }
-  for (int ks = 0; ks < KS2; ++ks)
-    for (int h = 0; h < 2; ++h)
-      for (int m = 0; m < out_dim; ++m)
-        for (int j = 0; j < 8; ++j)
-          w3f[((size_t)(ks * 2 * out_dim) + h * out_dim + m) * 8 + j] = bf16_rne(w->w3[(size_t)m * H + chained_k(ks, h, j)]);
+  pack_w2f(base + L.w2, w->w2, ToBf16());  // the trunk's tail: the actor's W2F and W3F
+  pack_w3f(base + L.w3, w->w3, out_dim, ToBf16());
   memcpy(base + L.b2, w->b2, H * 4);
   memcpy(base + L.b3, w->b3, (size_t)out_dim * 4);
   return SWARM_OK;

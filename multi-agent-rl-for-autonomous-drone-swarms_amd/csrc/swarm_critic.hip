@@ -370,25 +370,10 @@ int swarm_critic_pack(int in_dim, int precision, const float* w1, const float* b
   if (precision == SWARM_POLICY_BF16) {
     const Bf16Layout L(in_dim);
     unsigned char* base = static_cast<unsigned char*>(host_out);
-    uint16_t* w1f = reinterpret_cast<uint16_t*>(base);
-    uint16_t* w2f = reinterpret_cast<uint16_t*>(base + L.w2);
-    for (int c = 0; c < L.nc1; ++c)
-      for (int ks = 0; ks < KC; ++ks)
-        for (int ob = 0; ob < OB; ++ob)
-          for (int l = 0; l < 64; ++l)
-            for (int j = 0; j < 8; ++j) {
-              const int m = ob * 32 + (l & 31), k = 16 * (KC * c + ks) + 8 * (l >> 5) + j;
-              const float v = k < in_dim ? w1[(size_t)m * in_dim + k] : (k == in_dim ? b1[m] : 0.f);
-              w1f[((((size_t)c * KC + ks) * OB + ob) * 64 + l) * 8 + j] = bf16_rne(v);
-            }
-    for (int ob = 0; ob < OB; ++ob)
-      for (int ks = 0; ks < KS2; ++ks)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j)
-            w2f[(((size_t)ob * KS2 + ks) * 64 + l) * 8 + j] = bf16_rne(w2[(ob * 32 + (l & 31)) * H + chained_k(ks, l >> 5, j)]);
+    pack_w1f(base, w1, b1, in_dim, L.nc1 * KC, W1_KS_MAJOR, ToBf16());  // chunk c: k-steps KC c .. KC c + KC - 1
+    pack_w2f(base + L.w2, w2, ToBf16());  // chunk ob: the actor's W2F blocks of out block ob
     memcpy(base + L.b2, b2, H * 4);
-    float* w3f = reinterpret_cast<float*>(base + L.w3);
-    for (int m = 0; m < H; ++m) w3f[m] = bf16_to_f32(bf16_rne(w3[m]));
+    pack_w3_row(reinterpret_cast<float*>(base + L.w3), w3);
     memcpy(base + L.b3, b3, 4);
   } else {
     const F32Layout L(in_dim);

@@ -1,13 +1,18 @@
 // swarm_nn.h — what the network units (swarm_policy / swarm_attn / swarm_critic / swarm_value /
-// swarm_ppo .hip) must agree on, written once: the MFMA fragment geometry and the packers that
-// define the blob formats, the sampling noise, GAE, and the host-side error and grid helpers.
+// swarm_ppo / swarm_train .hip) must agree on, written once: the MFMA fragment geometry, the bf16
+// blob formats (the element rules that host and device share, the host packers that loop over
+// them, the actor blob's layout and dims check), the sampling noise, GAE, and the host-side error
+// and grid helpers.
 // Internal: not installed, not part of the C-ABI (include/swarm_mi355x.h); included as
 // "swarm_nn.h", next to the sources.  Everything has internal linkage: every unit compiles its own
 // copy, and a library may be linked from any subset of the units.
 //
 // Not here: the loops that stage a blob in LDS.  Outlined into a shared inline function they
 // compile to a different prologue on gfx950 (other address arithmetic and ordering), and attn's
-// differs anyway (it skips the W3 block): they stay in their kernels.
+// differs anyway (it skips the W3 block): they stay in their kernels.  Nor the
+// f32 blobs (chained_k_f32, the F32Layouts, the transposes), the other towers' layouts, the
+// attention packer's float64 folds and swarm_train.hip's transposed W2^T / W3^T fragments: each
+// has one user, or two with different layouts.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,24 +37,129 @@ constexpr int H = SWARM_POLICY_HIDDEN;  // 256
 constexpr int OB = H / 32;              // 8 out blocks of 32
 constexpr int KS2 = H / 16;             // 16 k-steps over the hidden dim
 constexpr int FRAG = 1024;              // bytes of one 64-lane x 16-B fragment block
+constexpr int KP1 = 48;                 // obs-tower bf16 layer-1 K (obs dim + bias column, padded)
+constexpr int KS1 = KP1 / 16;           // 3 k-steps
+static_assert(SWARM_POLICY_MAX_IN + 1 <= KP1, "the bias column sits inside the padded K");
 
-// ---------------------------------------------------------------- blob formats (host)
+// ---------------------------------------------------------------- blob formats: element rules (host and device)
 // hidden unit carried by k-step `ks` (of 16) of an accumulator-chained operand, lane half h, element j:
 // the accumulator's register order (swarm_policy.hip's header comment)
-inline int chained_k(int ks, int h, int j) { return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
+__host__ __device__ inline int chained_k(int ks, int h, int j) {
+  return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+}
 
-inline uint16_t bf16_rne(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
+__host__ __device__ inline uint16_t bf16_rne(float f) {
+  uint32_t u = __builtin_bit_cast(uint32_t, f);
   if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
   u += 0x7fffu + ((u >> 16) & 1u);
   return (uint16_t)(u >> 16);
 }
-inline float bf16_to_f32(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
+inline float bf16_to_f32(uint16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
+struct ToBf16 {  // the bf16 blobs' element conversion
+  __host__ __device__ uint16_t operator()(float v) const { return bf16_rne(v); }
+};
+
+// A fragment block is 64 lanes x 16 B: lane 32 h + n holds, as one 16-byte slot, the 8 elements j of
+// row n of the block's 32 at the 8 k columns of k-step ks that lane half h carries.
+// the slot of (block, row n, half h) among a region's slots, and back
+__host__ __device__ inline int frag_slot(int blk, int n, int h) { return blk * 64 + 32 * h + n; }
+struct FragSlot {
+  int blk, n, h;
+};
+__host__ __device__ inline FragSlot frag_slot_of(int s) { return {s >> 6, s & 31, (s >> 5) & 1}; }
+// W3F keeps only the `out` rows that exist: k-step ks, half h, logit m (the index of an element: 8 slot + j)
+__host__ __device__ inline int w3f_slot(int out, int ks, int h, int m) { return ks * 2 * out + h * out + m; }
+struct W3Slot {
+  int ks, h, m;
+};
+__host__ __device__ inline W3Slot w3f_slot_of(int out, int s) {
+  const int r = s % (2 * out);
+  return {s / (2 * out), r / out, r % out};
+}
+
+// layer 1 augmented: row m, column k of [W1 | b1 | 0]
+__host__ __device__ inline float l1_aug(const float* w1, const float* b1, int in, int m, int k) {
+  return k < in ? w1[m * in + k] : (k == in ? b1[m] : 0.f);
+}
+// the slot of row m, k-step ks, half h: layer 1 in natural k order ...
+template <class Cv>
+__host__ __device__ inline void l1_slot(uint16_t (&e)[8], const float* w1, const float* b1, int in, int m, int ks, int h,
+                                        Cv cv) {
+  for (int j = 0; j < 8; ++j) e[j] = cv(l1_aug(w1, b1, in, m, 16 * ks + 8 * h + j));
+}
+// ... and a [*, 256] matrix read by an accumulator-chained operand (W2, W3) in chained k order
+template <class Cv>
+__host__ __device__ inline void chained_slot(uint16_t (&e)[8], const float* w, int m, int ks, int h, Cv cv) {
+  for (int j = 0; j < 8; ++j) e[j] = cv(w[m * H + chained_k(ks, h, j)]);
+}
+
+// ---------------------------------------------------------------- blob formats: host packers
+// W1F: OB x nks blocks of the augmented layer 1; block (ob, ks) at ob nks + ks (the obs towers: the
+// kernels walk an out block's k-steps) or at ks OB + ob (the critic: it streams chunks of k-steps)
+enum W1Order { W1_OB_MAJOR, W1_KS_MAJOR };
+template <class Cv>
+inline void pack_w1f(unsigned char* dst, const float* w1, const float* b1, int in, int nks, W1Order order, Cv cv) {
+  uint16_t e[8];
+  for (int ob = 0; ob < OB; ++ob)
+    for (int ks = 0; ks < nks; ++ks)
+      for (int l = 0; l < 64; ++l) {
+        l1_slot(e, w1, b1, in, ob * 32 + (l & 31), ks, l >> 5, cv);
+        memcpy(dst + (size_t)frag_slot(order == W1_KS_MAJOR ? ks * OB + ob : ob * nks + ks, l & 31, l >> 5) * 16, e, 16);
+      }
+}
+// W2F: OB x KS2 blocks, block (ob, ks) at ob KS2 + ks
+template <class Cv>
+inline void pack_w2f(unsigned char* dst, const float* w2, Cv cv) {
+  uint16_t e[8];
+  for (int ob = 0; ob < OB; ++ob)
+    for (int ks = 0; ks < KS2; ++ks)
+      for (int l = 0; l < 64; ++l) {
+        chained_slot(e, w2, ob * 32 + (l & 31), ks, l >> 5, cv);
+        memcpy(dst + (size_t)frag_slot(ob * KS2 + ks, l & 31, l >> 5) * 16, e, 16);
+      }
+}
+// W3F: KS2 k-steps x 2 halves x out rows
+template <class Cv>
+inline void pack_w3f(unsigned char* dst, const float* w3, int out, Cv cv) {
+  uint16_t e[8];
+  for (int ks = 0; ks < KS2; ++ks)
+    for (int h = 0; h < 2; ++h)
+      for (int m = 0; m < out; ++m) {
+        chained_slot(e, w3, m, ks, h, cv);
+        memcpy(dst + (size_t)w3f_slot(out, ks, h, m) * 16, e, 16);
+      }
+}
+// the value towers' w3 row: bf16-rounded, kept as f32
+inline void pack_w3_row(float* dst, const float* w3) {
+  for (int m = 0; m < H; ++m) dst[m] = bf16_to_f32(bf16_rne(w3[m]));
+}
+
+// ---------------------------------------------------------------- the actor's bf16 blob
+// [W1F 8x3 blocks][W2F 8x16 blocks][W3F 16 k-steps x 2*out lanes x 16 B][b2 256 f32][b3 32 f32]:
+// swarm_policy_pack's bf16 blob (and, with f16 elements, each half of its f32x3 blob) and what
+// swarm_train.hip's device packer writes
+struct ActorLayout {
+  int out;
+  size_t w1, w2, w3, b2, b3, total;
+  __host__ __device__ explicit ActorLayout(int o) : out(o) {
+    w1 = 0;
+    w2 = w1 + (size_t)OB * KS1 * FRAG;
+    w3 = w2 + (size_t)OB * KS2 * FRAG;
+    b2 = w3 + (size_t)KS2 * 2 * o * 16;
+    b3 = b2 + H * 4;
+    total = b3 + 32 * 4;
+  }
+};
+inline bool actor_dims_ok(int in_dim, int out_dim) {
+  return in_dim >= 1 && in_dim <= SWARM_POLICY_MAX_IN && out_dim >= 2 && out_dim <= SWARM_POLICY_MAX_OUT && !(out_dim & 1);
+}
+// the three fragment regions of one blob at `base`
+template <class Cv>
+inline void pack_actor_frags(unsigned char* base, const ActorLayout& L, int in, const float* w1, const float* b1,
+                             const float* w2, const float* w3, Cv cv) {
+  pack_w1f(base + L.w1, w1, b1, in, KS1, W1_OB_MAJOR, cv);
+  pack_w2f(base + L.w2, w2, cv);
+  pack_w3f(base + L.w3, w3, L.out, cv);
 }
 
 // ---------------------------------------------------------------- accumulators -> bf16 fragment (device)

@@ -36,23 +36,8 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int KP1 = 48;                 // bf16 layer-1 K (obs dim + bias column, padded)
-constexpr int KS1 = KP1 / 16;           // 3 k-steps
-
 // ---------------------------------------------------------------- packed blob layouts
-// bf16: [W1F 8x3 blocks][W2F 8x16 blocks][W3F 16 k-steps x 2*out lanes x 16 B][b2 256 f32][b3 32 f32]
-struct Bf16Layout {
-  int out;
-  size_t w1, w2, w3, b2, b3, total;
-  __host__ __device__ explicit Bf16Layout(int o) : out(o) {
-    w1 = 0;
-    w2 = w1 + (size_t)OB * KS1 * FRAG;
-    w3 = w2 + (size_t)OB * KS2 * FRAG;
-    b2 = w3 + (size_t)KS2 * 2 * o * 16;
-    b3 = b2 + H * 4;
-    total = b3 + 32 * 4;
-  }
-};
+// bf16 and each half of f32x3: swarm_nn.h's ActorLayout
 // f32: [W1 16 obs x KQ1 q x 64 lanes][W2 16 x 64 x 64][W3 64 x 64][b2 256][b3 16] floats
 struct F32Layout {
   int kq1;
@@ -128,7 +113,7 @@ template <int WAVES, int MODE, int T, int IN_C = 0, int OUT_C = 0>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4 > 0 ? WAVES / 4 : 1)))
 policy_mlp_bf16(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const Bf16Layout L(A.out);
+  const ActorLayout L(A.out);
   {  // stage the packed weights (~159 KB) in LDS, once per workgroup: 8 loads in flight per
      // thread per round (a load-then-store loop pays one global round trip per 16 B x threads)
     const int4* src = reinterpret_cast<const int4*>(A.w);
@@ -477,7 +462,7 @@ template <int WAVES, int MODE, int IN_C = 0, int OUT_C = 0>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4 > 0 ? WAVES / 4 : 1)))
 policy_mlp_x3(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const Bf16Layout L(A.out);
+  const ActorLayout L(A.out);
   {  // stage the hi blob (f16 fragments + f32 biases, ~159 KB) in LDS, once per workgroup
     const int4* src = reinterpret_cast<const int4*>(A.w);
     int4* dst = reinterpret_cast<int4*>(lds);
@@ -730,7 +715,7 @@ template <int WAVES, int MODE>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4 > 0 ? WAVES / 4 : 1)))
 policy_mlp_x3l(const FwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const Bf16Layout L(A.out);
+  const ActorLayout L(A.out);
   {  // stage the hi blob in LDS, once per workgroup (as policy_mlp_x3)
     const int4* src = reinterpret_cast<const int4*>(A.w);
     int4* dst = reinterpret_cast<int4*>(lds);
@@ -925,10 +910,10 @@ extern "C" {
 const char* swarm_policy_last_error(void) { return g_err.msg; }
 
 long long swarm_policy_packed_bytes(int in_dim, int out_dim, int precision) {
-  if (in_dim < 1 || in_dim > SWARM_POLICY_MAX_IN || out_dim < 2 || out_dim > SWARM_POLICY_MAX_OUT || (out_dim & 1))
+  if (!actor_dims_ok(in_dim, out_dim))
     return g_err.fail(SWARM_ELIMIT, "policy dims out of range"), (long long)SWARM_ELIMIT;
-  if (precision == SWARM_POLICY_BF16) return (long long)Bf16Layout(out_dim).total;
-  if (precision == SWARM_POLICY_F32X3) return 2 * (long long)Bf16Layout(out_dim).total;  // hi blob, lo blob
+  if (precision == SWARM_POLICY_BF16) return (long long)ActorLayout(out_dim).total;
+  if (precision == SWARM_POLICY_F32X3) return 2 * (long long)ActorLayout(out_dim).total;  // hi blob, lo blob
   if (precision == SWARM_POLICY_F32) return (long long)F32Layout(in_dim).total * 4;
   return g_err.fail(SWARM_EINVAL, "unknown precision"), (long long)SWARM_EINVAL;
 }
@@ -950,65 +935,17 @@ int swarm_policy_pack(int in_dim, int out_dim, int precision, const float* w1, c
       return g_err.fail(SWARM_EINVAL, "f32x3 weights outside the f16 range (W1, b1, W2, W3 must be finite and round to at most 65504)");
   }
   memset(host_out, 0, (size_t)nb);
-  if (precision == SWARM_POLICY_F32X3) {
-    // the bf16 blob's fragment order twice, f16 elements: hi = f16(v), then lo = f16((v - hi) 2^11)
-    const Bf16Layout L(out_dim);
-    for (int part = 0; part < 2; ++part) {
-      unsigned char* base = static_cast<unsigned char*>(host_out) + part * L.total;
-      auto cv = [part](float v) -> uint16_t {
-        const uint16_t hi = f16_rne(v);
-        return part == 0 ? hi : f16_rne((v - f16_to_f32(hi)) * 2048.f);  // lo scaled by 2^11 (kernel: X3_LO_SCALE)
-      };
-      uint16_t* w1f = reinterpret_cast<uint16_t*>(base + L.w1);
-      uint16_t* w2f = reinterpret_cast<uint16_t*>(base + L.w2);
-      uint16_t* w3f = reinterpret_cast<uint16_t*>(base + L.w3);
-      for (int ob = 0; ob < OB; ++ob)
-        for (int l = 0; l < 64; ++l) {
-          const int m = ob * 32 + (l & 31), h = l >> 5;
-          for (int ks = 0; ks < KS1; ++ks)
-            for (int j = 0; j < 8; ++j) {
-              const int k = 16 * ks + 8 * h + j;
-              const float v = k < in_dim ? w1[m * in_dim + k] : (k == in_dim ? b1[m] : 0.f);
-              w1f[((ob * KS1 + ks) * 64 + l) * 8 + j] = cv(v);
-            }
-          for (int ks = 0; ks < KS2; ++ks)
-            for (int j = 0; j < 8; ++j) w2f[((ob * KS2 + ks) * 64 + l) * 8 + j] = cv(w2[m * H + chained_k(ks, h, j)]);
-        }
-      for (int ks = 0; ks < KS2; ++ks)
-        for (int h = 0; h < 2; ++h)
-          for (int m = 0; m < out_dim; ++m)
-            for (int j = 0; j < 8; ++j)
-              w3f[((ks * 2 * out_dim) + h * out_dim + m) * 8 + j] = cv(w3[m * H + chained_k(ks, h, j)]);
-      if (part == 0) {
-        memcpy(base + L.b2, b2, H * 4);
-        memcpy(base + L.b3, b3, (size_t)out_dim * 4);
-      }
-    }
-  } else if (precision == SWARM_POLICY_BF16) {
-    const Bf16Layout L(out_dim);
+  if (precision != SWARM_POLICY_F32) {
+    const ActorLayout L(out_dim);
     unsigned char* base = static_cast<unsigned char*>(host_out);
-    uint16_t* w1f = reinterpret_cast<uint16_t*>(base + L.w1);
-    uint16_t* w2f = reinterpret_cast<uint16_t*>(base + L.w2);
-    uint16_t* w3f = reinterpret_cast<uint16_t*>(base + L.w3);
-    for (int ob = 0; ob < OB; ++ob)
-      for (int l = 0; l < 64; ++l) {
-        const int m = ob * 32 + (l & 31), h = l >> 5;
-        for (int ks = 0; ks < KS1; ++ks)
-          for (int j = 0; j < 8; ++j) {
-            const int k = 16 * ks + 8 * h + j;
-            const float v = k < in_dim ? w1[m * in_dim + k] : (k == in_dim ? b1[m] : 0.f);
-            w1f[((ob * KS1 + ks) * 64 + l) * 8 + j] = bf16_rne(v);
-          }
-        for (int ks = 0; ks < KS2; ++ks)
-          for (int j = 0; j < 8; ++j)
-            w2f[((ob * KS2 + ks) * 64 + l) * 8 + j] = bf16_rne(w2[m * H + chained_k(ks, h, j)]);
-      }
-    for (int ks = 0; ks < KS2; ++ks)
-      for (int h = 0; h < 2; ++h)
-        for (int m = 0; m < out_dim; ++m)
-          for (int j = 0; j < 8; ++j)
-            w3f[((ks * 2 * out_dim) + h * out_dim + m) * 8 + j] = bf16_rne(w3[m * H + chained_k(ks, h, j)]);
-    memcpy(base + L.b2, b2, H * 4);
+    if (precision == SWARM_POLICY_BF16) pack_actor_frags(base, L, in_dim, w1, b1, w2, w3, ToBf16());
+    else  // f32x3: the bf16 blob's fragment order twice, f16 elements: hi = f16(v), then lo = f16((v - hi) 2^11)
+      for (int part = 0; part < 2; ++part)
+        pack_actor_frags(base + part * L.total, L, in_dim, w1, b1, w2, w3, [part](float v) -> uint16_t {
+          const uint16_t hi = f16_rne(v);
+          return part == 0 ? hi : f16_rne((v - f16_to_f32(hi)) * 2048.f);  // lo scaled by 2^11 (kernel: X3_LO_SCALE)
+        });
+    memcpy(base + L.b2, b2, H * 4);  // b2, b3 stay f32 (f32x3: in the hi blob)
     memcpy(base + L.b3, b3, (size_t)out_dim * 4);
   } else {
     const F32Layout L(in_dim);
@@ -1058,7 +995,7 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
   a.ctr_hi = (uint32_t)(counter >> 32);
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->precision == SWARM_POLICY_BF16) {
-    const int lds = (int)Bf16Layout(p->out_dim).total;
+    const int lds = (int)ActorLayout(p->out_dim).total;
     const bool dflt = p->in_dim == 37 && p->out_dim == 6;  // K = 3, Ms = 4 obs; 3-d Gaussian actions
     auto fn = action_mode == SWARM_POLICY_ACT_SAMPLE
                   ? (dflt ? policy_mlp_bf16<BF16_WAVES_T, SWARM_POLICY_ACT_SAMPLE, BF16_TILES, 37, 6>
@@ -1071,7 +1008,7 @@ int swarm_policy_forward(const swarm_policy_t* p, const float* obs, long long ro
     const int grid = tile_grid(BF16_WAVES_T, ((rows + 31) / 32 + BF16_TILES - 1) / BF16_TILES);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * BF16_WAVES_T), lds, s, a);
   } else if (p->precision == SWARM_POLICY_F32X3) {
-    const int lds = (int)Bf16Layout(p->out_dim).total;
+    const int lds = (int)ActorLayout(p->out_dim).total;
     const bool dflt = p->in_dim == 37 && p->out_dim == 6;
     (void)dflt;  // the compile-time-dims instance spills (71 VGPRs at 512); the runtime-dims one fits (492)
     const char* pipe = getenv("SWARM_POLICY_X3_PIPELINED");

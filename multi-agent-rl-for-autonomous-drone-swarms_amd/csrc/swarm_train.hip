@@ -1,7 +1,10 @@
 // swarm_train.hip — training the bf16 actor on the device (gfx950, MFMA): the backward of
 // swarm_policy.hip's bf16 MLP, its weight gradients, and a device packer that turns the float32
 // master weights back into the inference blob.  The arithmetic is written out in
-// include/swarm_mi355x.h; this file says how it is laid out.
+// include/swarm_mi355x.h; this file says how it is laid out.  The blob's layout (ActorLayout) and
+// the rules for its fragment elements are swarm_nn.h's, the ones swarm_policy_pack loops over: the
+// packer here only maps a thread to a slot.  The transposed W2^T / W3^T fragments of the workspace
+// have no other user and are defined here.
 //
 // Five simple launches per swarm_policy_backward, all async on one stream, no atomics, no grid that
 // depends on the device:
@@ -37,8 +40,6 @@
 
 namespace {
 
-constexpr int KP1 = 48;        // bf16 layer-1 K (obs dim + bias column, padded): swarm_policy.hip's
-constexpr int KS1 = KP1 / 16;  // 3 k-steps
 constexpr int XU = 64;         // unit-major rows of x (two 32-blocks: columns 0..D-1, the 1, zeros)
 constexpr int GU = 32;         // unit-major rows of g (one 32-block: 2A columns, zeros)
 constexpr int TRAIN_WAVES = 8;       // waves per workgroup of (a) and (b): one workgroup per CU (the LDS blob)
@@ -48,21 +49,6 @@ constexpr size_t W1F_BYTES = (size_t)OB * KS1 * FRAG;     // 24,576
 constexpr size_t W2F_BYTES = (size_t)OB * KS2 * FRAG;     // 131,072
 constexpr size_t W3T_BYTES = (size_t)OB * FRAG;           // 8,192
 constexpr int PART_FLOATS = H * H + H + GU * H + GU + H * XU;  // one slab's partials: P2, PB2, P3, PB3, P1
-
-// swarm_policy_pack's bf16 blob: [W1F 8x3 blocks][W2F 8x16 blocks][W3F 16 k-steps x 2*out lanes x 16 B][b2][b3 32 f32]
-// (swarm_policy.hip keeps its own copy of this struct in its unnamed namespace; the packer test holds
-// the two to the same bytes at the smallest, the default and the widest logits)
-struct Bf16Layout {
-  size_t w1, w2, w3, b2, b3, total;
-  __host__ __device__ explicit Bf16Layout(int o) {
-    w1 = 0;
-    w2 = w1 + W1F_BYTES;
-    w3 = w2 + W2F_BYTES;
-    b2 = w3 + (size_t)KS2 * 2 * o * 16;
-    b3 = b2 + H * 4;
-    total = b3 + 32 * 4;
-  }
-};
 
 // the training workspace (bytes): the transposed fragment blobs the packer writes, the per-row
 // stage tensors of one backward (ld = rows rounded up to 32), the slabs' partial sums
@@ -86,17 +72,6 @@ struct TrainLayout {
   }
 };
 
-// swarm_nn.h's bf16_rne on the device: the same integer arithmetic, so the same bytes
-__device__ __forceinline__ uint16_t bf16_rne_dev(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ int chained_k_dev(int ks, int h, int j) {
-  return (ks >> 1) * 32 + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-}
-
 // ---------------------------------------------------------------- device packer
 struct PackArgs {
   const float *w1, *b1, *w2, *b2, *w3, *b3;
@@ -107,7 +82,7 @@ struct PackArgs {
 
 // one thread per 16-byte slot (8 bf16 or 4 f32) of the blob, then of W2^T and W3^T
 __global__ void __launch_bounds__(256) train_pack(const PackArgs A) {
-  const Bf16Layout L(A.out);
+  const ActorLayout L(A.out);
   const TrainLayout T(0);
   const int nblob = (int)(L.total / 16);
   const int nw2t = (int)(W2F_BYTES / 16), nw3t = (int)(W3T_BYTES / 16);
@@ -130,37 +105,29 @@ __global__ void __launch_bounds__(256) train_pack(const PackArgs A) {
       *reinterpret_cast<uint4*>(dst) = v;
       return;
     }
-    if (off >= L.w3) {  // W3F: slot = ks * 2 out + h out + m, chained k
-      const int s3 = (int)((off - L.w3) / 16);
-      const int ks = s3 / (2 * A.out), r = s3 % (2 * A.out), h = r / A.out, m = r % A.out;
-      for (int j = 0; j < 8; ++j) e[j] = bf16_rne_dev(A.w3[m * H + chained_k_dev(ks, h, j)]);
-    } else if (off >= L.w2) {  // W2F: block (ob, ks), lane l, chained k
-      const int s2 = (int)((off - L.w2) / 16);
-      const int l = s2 & 63, blk = s2 >> 6, ob = blk / KS2, ks = blk % KS2;
-      const int m = ob * 32 + (l & 31), h = l >> 5;
-      for (int j = 0; j < 8; ++j) e[j] = bf16_rne_dev(A.w2[m * H + chained_k_dev(ks, h, j)]);
-    } else {  // W1F: block (ob, ks), lane l, natural k, b1 in column `in`
-      const int l = slot & 63, blk = slot >> 6, ob = blk / KS1, ks = blk % KS1;
-      const int m = ob * 32 + (l & 31), h = l >> 5;
-      for (int j = 0; j < 8; ++j) {
-        const int k = 16 * ks + 8 * h + j;
-        e[j] = bf16_rne_dev(k < A.in ? A.w1[m * A.in + k] : (k == A.in ? A.b1[m] : 0.f));
-      }
+    // the blob's fragments: swarm_nn.h's slots and element rules, as the host packers
+    if (off >= L.w3) {
+      const W3Slot f = w3f_slot_of(A.out, (int)((off - L.w3) / 16));
+      chained_slot(e, A.w3, f.m, f.ks, f.h, ToBf16());
+    } else if (off >= L.w2) {  // W2F: block ob KS2 + ks
+      const FragSlot f = frag_slot_of((int)((off - L.w2) / 16));
+      chained_slot(e, A.w2, f.blk / KS2 * 32 + f.n, f.blk % KS2, f.h, ToBf16());
+    } else {  // W1F: block ob KS1 + ks
+      const FragSlot f = frag_slot_of(slot);
+      l1_slot(e, A.w1, A.b1, A.in, f.blk / KS1 * 32 + f.n, f.blk % KS1, f.h, ToBf16());
     }
   } else if (slot < nblob + nw2t) {  // W2^T fragments: block (ib, ks), lane l: W2[16 ks + 8 h + j][32 ib + (l & 31)]
-    const int s = slot - nblob;
-    dst = A.ws + T.w2t + (size_t)s * 16;
-    const int l = s & 63, blk = s >> 6, ib = blk / KS2, ks = blk % KS2;
-    const int i = ib * 32 + (l & 31), h = l >> 5;
-    for (int j = 0; j < 8; ++j) e[j] = bf16_rne_dev(A.w2[(16 * ks + 8 * h + j) * H + i]);
+    const FragSlot f = frag_slot_of(slot - nblob);
+    dst = A.ws + T.w2t + (size_t)(slot - nblob) * 16;
+    const int i = f.blk / KS2 * 32 + f.n, ks = f.blk % KS2;
+    for (int j = 0; j < 8; ++j) e[j] = bf16_rne(A.w2[(16 * ks + 8 * f.h + j) * H + i]);
   } else {  // W3^T fragments: block ob, lane l: W3[8 h + j][32 ob + (l & 31)], zero past `out`
-    const int s = slot - nblob - nw2t;
-    dst = A.ws + T.w3t + (size_t)s * 16;
-    const int l = s & 63, ob = s >> 6;
-    const int u = ob * 32 + (l & 31), h = l >> 5;
+    const FragSlot f = frag_slot_of(slot - nblob - nw2t);
+    dst = A.ws + T.w3t + (size_t)(slot - nblob - nw2t) * 16;
+    const int u = f.blk * 32 + f.n;
     for (int j = 0; j < 8; ++j) {
-      const int m = 8 * h + j;
-      e[j] = m < A.out ? bf16_rne_dev(A.w3[m * H + u]) : (uint16_t)0;
+      const int m = 8 * f.h + j;
+      e[j] = m < A.out ? bf16_rne(A.w3[m * H + u]) : (uint16_t)0;
     }
   }
   v = make_uint4(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16), e[4] | ((uint32_t)e[5] << 16),
@@ -238,7 +205,7 @@ __device__ __forceinline__ void stage(int4* dst, const int4* src, int n16) {
 __global__ void __launch_bounds__(64 * TRAIN_WAVES) __attribute__((amdgpu_waves_per_eu(2)))
 train_fwd_dz2(const BwdArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const Bf16Layout L(A.out);
+  const ActorLayout L(A.out);
   const TrainLayout T(A.rows);
   stage(reinterpret_cast<int4*>(lds), reinterpret_cast<const int4*>(A.blob), (int)((W1F_BYTES + W2F_BYTES) / 16));
   stage(reinterpret_cast<int4*>(lds + W1F_BYTES + W2F_BYTES), reinterpret_cast<const int4*>(A.blob + L.b2), H * 4 / 16);
@@ -518,9 +485,7 @@ __global__ void __launch_bounds__(256) train_finalise(const FinArgs A) {
 thread_local UnitError g_err;
 
 int check_dims(int in_dim, int out_dim) {
-  if (in_dim < 1 || in_dim > SWARM_POLICY_MAX_IN || out_dim < 2 || out_dim > SWARM_POLICY_MAX_OUT || (out_dim & 1))
-    return g_err.fail(SWARM_ELIMIT, "policy dims out of range");
-  return SWARM_OK;
+  return actor_dims_ok(in_dim, out_dim) ? SWARM_OK : g_err.fail(SWARM_ELIMIT, "policy dims out of range");
 }
 
 }  // namespace
@@ -544,7 +509,7 @@ int swarm_policy_pack_device(int in_dim, int out_dim, const float* w1, const flo
     return g_err.fail(SWARM_EINVAL, "weights and workspace must be 16-B aligned");
   const PackArgs a{w1, b1, w2, b2, w3, b3, static_cast<unsigned char*>(weights), static_cast<unsigned char*>(workspace),
                    in_dim, out_dim};
-  const int slots = (int)((Bf16Layout(out_dim).total + W2F_BYTES + W3T_BYTES) / 16);
+  const int slots = (int)((ActorLayout(out_dim).total + W2F_BYTES + W3T_BYTES) / 16);
   hipLaunchKernelGGL(train_pack, dim3((slots + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, a);
   return g_err.launch_status();
 }

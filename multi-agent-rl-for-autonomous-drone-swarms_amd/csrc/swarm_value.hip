@@ -38,10 +38,6 @@
 
 namespace {
 
-constexpr int KP1 = 48;                 // layer-1 K (obs dim + bias column, padded)
-constexpr int KS1 = KP1 / 16;           // 3 k-steps
-static_assert(SWARM_POLICY_MAX_IN + 1 <= KP1, "the bias column sits inside the padded K");
-
 // bf16 blob: [W1F 8 x 3 blocks][W2F 8 x 16 blocks][b2 256 f32][w3 256 f32, bf16-rounded][b3, 4 f32]
 constexpr size_t L_W1 = 0;
 constexpr size_t L_W2 = L_W1 + (size_t)OB * KS1 * FRAG;
@@ -204,23 +200,10 @@ int swarm_value_pack(int in_dim, int precision, const float* w1, const float* b1
   if (precision == SWARM_POLICY_F32) return vcritic(swarm_critic_pack(in_dim, precision, w1, b1, w2, b2, w3, b3, host_out));
   memset(host_out, 0, (size_t)nb);
   unsigned char* base = static_cast<unsigned char*>(host_out);
-  uint16_t* w1f = reinterpret_cast<uint16_t*>(base + L_W1);
-  uint16_t* w2f = reinterpret_cast<uint16_t*>(base + L_W2);
-  for (int ob = 0; ob < OB; ++ob)
-    for (int l = 0; l < 64; ++l) {
-      const int m = ob * 32 + (l & 31), h = l >> 5;
-      for (int ks = 0; ks < KS1; ++ks)
-        for (int j = 0; j < 8; ++j) {
-          const int k = 16 * ks + 8 * h + j;
-          const float v = k < in_dim ? w1[m * in_dim + k] : (k == in_dim ? b1[m] : 0.f);
-          w1f[((ob * KS1 + ks) * 64 + l) * 8 + j] = bf16_rne(v);
-        }
-      for (int ks = 0; ks < KS2; ++ks)
-        for (int j = 0; j < 8; ++j) w2f[((ob * KS2 + ks) * 64 + l) * 8 + j] = bf16_rne(w2[m * H + chained_k(ks, h, j)]);
-    }
+  pack_w1f(base + L_W1, w1, b1, in_dim, KS1, W1_OB_MAJOR, ToBf16());  // the actor's W1F
+  pack_w2f(base + L_W2, w2, ToBf16());
   memcpy(base + L_B2, b2, H * 4);
-  float* w3f = reinterpret_cast<float*>(base + L_W3);
-  for (int m = 0; m < H; ++m) w3f[m] = bf16_to_f32(bf16_rne(w3[m]));
+  pack_w3_row(reinterpret_cast<float*>(base + L_W3), w3);
   memcpy(base + L_B3, b3, 4);
   return SWARM_OK;
 }
