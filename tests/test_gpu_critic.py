@@ -15,6 +15,7 @@ Tolerances:
         against float64 over the in_dim's input set (computed here from the references, never
         from the kernel; 0.004-0.009 on |v| up to 2).
 The second-grid-pass cases mirror the per-CU grid caps of swarm_critic_forward (GRID below).
+The bit-exact layer of the bf16 path (rounding rules, format, no tolerance) is tests/test_gpu_bf16_exact.py.
 """
 from __future__ import annotations
 

@@ -10,6 +10,7 @@ Tolerances (stated per path):
        (two waves per SIMD, default; one wave pipelined) agree bit for bit
   bf16 (v_mfma_f32_32x32x16_bf16): within 0.02 of the NumPy emulation of the same bf16 arithmetic
        (tests/test_policy_cpu.py) and within 0.3 of the f32 graph (logits span about -37 .. 66).
+The bit-exact layer of the bf16 path (rounding rules, format, no tolerance) is tests/test_gpu_bf16_exact.py.
 """
 from __future__ import annotations
 

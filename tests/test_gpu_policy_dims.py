@@ -26,6 +26,7 @@ rounding, 2^-24 |a| exp(-log_std), and expf's ulps on z.  Bound:
 Measured maximum of |z - z_ref| on an MI355X over every case below: 8.298e-7 (MEASURED_Z_ERR; at
 most 0.052 of the bound).  Measured bf16 logits against the emulation: at most 1.078e-4 ((31, 12),
 one flipped bf16 activation at rows = 257; 1e-7 where none flips).
+The bit-exact layer of the bf16 path (rounding rules, format, no tolerance) is tests/test_gpu_bf16_exact.py.
 """
 from __future__ import annotations
 

@@ -19,6 +19,7 @@ Tolerances:
         against float64 over the in_dim's input set (computed here from the references, never
         from the kernel).
 The second-grid-pass case mirrors the grid of swarm_value_forward (GRID below).
+The bit-exact layer of the bf16 path (rounding rules, format, no tolerance) is tests/test_gpu_bf16_exact.py.
 """
 from __future__ import annotations
 
